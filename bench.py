@@ -9,10 +9,18 @@ Counted env-steps = tasks x num_processes x num_steps per step (eval steps are n
 like the reference's FPS print, morl/mopg.py:159).
 
     python bench.py [--gpus N --steps K --warmup W]       # N > 1: starts the N ranks itself
+    python bench.py --full [...]                          # + every secondary leg (below)
     python -m torch.distributed.run --nproc-per-node N --master-addr 127.0.0.1 bench.py --gpus N
 
-At N > 1 the headline line is weak scaling (--tasks per GPU) and carries a second timed leg, `strong`: the
-fixed population --strong-tasks (40) split over the ranks in task blocks (40 -> 20 / 10 / 5 per GPU).
+A plain run sets up, runs W warm-up steps, times exactly K steps and prints one JSON line (the headline figure, the
+update kernel's achieved FLOP rate from the same timed steps, the HV of the run's own offspring).  --dump-outputs DIR
+also writes what the last timed step computed (objective vectors, parameters, Adam moments, running statistics) as
+DIR/<name>.npy; the inputs are seeded, so two builds can be compared output for output.
+
+--full adds everything else: the whole PG-MORL run (`whole_run`, at N = 1), the CPU oracle processes
+(`cpu_baseline`), the committed device-vs-oracle HV comparison and PMC / SQ summaries quoted beside the roofline,
+and at N > 1 a second timed leg, `strong`: the fixed population --strong-tasks (40) split over the ranks in task
+blocks (40 -> 20 / 10 / 5 per GPU) beside the weak-scaling headline (--tasks per GPU).
 """
 import argparse
 import glob
@@ -41,6 +49,13 @@ def parse():
                          'torch.distributed.run it must equal WORLD_SIZE (default: WORLD_SIZE, else 1)')
     ap.add_argument('--steps', type=int, default=5)
     ap.add_argument('--warmup', type=int, default=2)
+    ap.add_argument('--full', action='store_true',
+                    help='also run every secondary leg: whole_run, cpu_baseline, the strong-scaling leg at N > 1, and '
+                         'quote the committed HV comparison and PMC / SQ summaries (off: the headline figure only)')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='after the timed steps, write what the last timed step computed (objs, params, Adam moments, '
+                         'running statistics) as DIR/<name>.npy (float32 / float64, at most 64 MB in all; a fixed '
+                         'seeded sample of anything larger; <name>_rank<r>.npy for ranks r > 0)')
     ap.add_argument('--env-name', default='MO-Walker2d-v2')
     ap.add_argument('--tasks', type=int, default=40,
                     help='tasks (policies) per GPU (--scaling weak) or in total (--scaling strong)')
@@ -56,22 +71,27 @@ def parse():
     ap.add_argument('--cpu-procs', type=int, default=15,
                     help='concurrent oracle processes: the 16-core host share of one GPU on the box minus the '
                          'bench process itself (the box allows 16 processes with the GPU open)')
-    ap.add_argument('--no-cpu-baseline', action='store_true')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='with --full: skip cpu_baseline')
     ap.add_argument('--no-overlap-eval', action='store_true', help='evaluate on the main stream (A/B)')
     ap.add_argument('--whole-run', dest='whole_run', action='store_true', default=None,
-                    help='also time the whole PG-MORL run (pgmorl_amd.morl.run: warm-up, generations, selection, '
-                         'writer) on Walker pop=40 with the reference budget (default: on at N=1)')
+                    help='with --full: also time the whole PG-MORL run (pgmorl_amd.morl.run: warm-up, generations, '
+                         'selection, writer) on Walker pop=40 with the reference budget (default: on at N=1)')
     ap.add_argument('--no-whole-run', dest='whole_run', action='store_false')
     ap.add_argument('--whole-run-steps', type=float, default=5e6,
                     help='--num-env-steps of the whole run (per task; scripts/walker2d-v2.py:38 uses 5e6)')
     ap.add_argument('--traffic-file', default=None,
-                    help='PMC summary (scripts/pmc_summary.py) to quote as roofline.traffic; default: the newest '
-                         'profiles/r0*_pmc_*.json whose workload matches this run')
+                    help='with --full: PMC summary (scripts/pmc_summary.py) to quote as roofline.traffic; default: '
+                         'the entry of profiles/pmc_head.json whose workload matches this run')
     ap.add_argument('--strong-tasks', type=int, default=40,
                     help='global population of the strong-scaling leg (split over the ranks in task blocks)')
-    ap.add_argument('--no-strong', action='store_true', help='skip the strong-scaling leg at N > 1')
+    ap.add_argument('--no-strong', action='store_true', help='with --full: skip the strong-scaling leg at N > 1')
     ap.add_argument('--stub-cpu', action='store_true', help=argparse.SUPPRESS)  # launcher tests (gloo, no GPU)
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error('--steps must be >= 1 and --warmup >= 0')
+    if not args.full and (args.whole_run or args.traffic_file):
+        ap.error('--whole-run / --traffic-file belong to the secondary legs: add --full')
+    return args
 
 
 def mflops_per_row(O, A, K, H=64):
@@ -278,14 +298,14 @@ def hv_comparison(env_name):
 
 def hypervolume(args, history, budget):
     """HV of the EP over every offspring objective vector this run produced (morl/ep.py:23-31,
-    morl/hypervolume.py), plus the committed device-vs-oracle comparison of the whole algorithm at an equal
-    budget (hv_comparison), when one exists for this env."""
+    morl/hypervolume.py), plus (--full) the committed device-vs-oracle comparison of the whole algorithm at an
+    equal budget (hv_comparison), when one exists for this env."""
     from pgmorl_amd import pareto
     objs = torch.cat(history).cpu().numpy()
     idx = pareto.get_ep_indices(objs)
     hv = {'hv': pareto.compute_hypervolume(objs[idx]) if len(idx) else 0.0, 'ep_size': len(idx),
           'budget_env_steps': budget, 'rng': 'perf-mode device streams', 'ref_point': 0}
-    cmp_ = hv_comparison(args.env_name)
+    cmp_ = hv_comparison(args.env_name) if args.full else None
     if cmp_ is not None:
         hv['vs_oracle_equal_budget'] = cmp_
     return hv
@@ -477,6 +497,27 @@ def launch_ranks(n):
     return rc
 
 
+# --dump-outputs: the TaskBatch state one iteration leaves its caller, beside the objective vectors (fp32 parameters and
+# Adam moments, fp64 running statistics)
+DUMP_STATE = ('params', 'adam_m', 'adam_v', 'ob_mean', 'ob_var', 'ob_count', 'ret_mean', 'ret_var', 'ret_count',
+              'obj_mean', 'obj_var', 'obj_count')
+DUMP_MAX_BYTES = 60_000_000  # under 64 MB with the .npy headers
+
+
+def dump_outputs(path, outputs, rank):
+    """Write ``outputs`` ({name: array}) as path/<name>.npy (<name>_rank<r>.npy for ranks r > 0), float32 / float64.
+    The files hold at most DUMP_MAX_BYTES in all: an array over its equal share is cut to a fixed seeded sample of
+    its elements (the same indices in every run of the same arguments)."""
+    os.makedirs(path, exist_ok=True)
+    share = DUMP_MAX_BYTES // max(1, len(outputs))
+    for name, a in outputs.items():
+        a = np.ascontiguousarray(a, dtype=np.float32 if a.dtype == np.float32 else np.float64)
+        if a.nbytes > share:
+            idx = np.sort(np.random.default_rng(0).choice(a.size, share // a.itemsize, replace=False))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(path, name + (f'_rank{rank}' if rank else '') + '.npy'), a)
+
+
 def _gather_ints(x, dev):
     """All-gather one int per rank (list form: works on gloo and RCCL)."""
     t = torch.tensor([x], dtype=torch.int64, device=dev)
@@ -569,9 +610,14 @@ def leg_gpu(args, spec, dev, rank, world, blocks, tag):
     upd_ms = float(np.mean([s.elapsed_time(e) for s, e in ev])) if ev else 0.0
     dt, upd_ms = allreduce_max([dt, upd_ms], dev)  # the slowest rank defines the step
     kernel = tb.update_variant() if tb is not None else None  # the launcher's own choice (pgm_ppo_update_variant)
+    outputs = None
+    if args.dump_outputs:  # what the last timed step left its caller (after the timed region; the device is idle)
+        outputs = {'objs': history[-1].cpu().numpy()}
+        if tb is not None:
+            outputs.update({name: getattr(tb, name).cpu().numpy() for name in DUMP_STATE})
     del tb
     torch.cuda.empty_cache()
-    return {'dt': dt, 'upd_ms': upd_ms, 'P': P, 'history': history, 'kernel': kernel, 'tag': tag}
+    return {'dt': dt, 'upd_ms': upd_ms, 'P': P, 'history': history, 'kernel': kernel, 'tag': tag, 'outputs': outputs}
 
 
 def leg_stub(args, spec, dev, rank, world, blocks, tag):
@@ -608,7 +654,8 @@ def leg_stub(args, spec, dev, rank, world, blocks, tag):
     dt, upd_ms = allreduce_max([time.perf_counter() - t0, 0.0], dev)
     assert all(h.shape[0] == G for h in history)
     assert all(torch.equal(h[:, 0], torch.arange(G, dtype=torch.float64) + i) for i, h in enumerate(history))
-    return {'dt': dt, 'upd_ms': upd_ms, 'P': P, 'history': history, 'kernel': 'stub', 'tag': tag}
+    outputs = {'objs': history[-1].numpy()} if args.dump_outputs else None
+    return {'dt': dt, 'upd_ms': upd_ms, 'P': P, 'history': history, 'kernel': 'stub', 'tag': tag, 'outputs': outputs}
 
 
 def main():
@@ -659,10 +706,12 @@ def main():
     dt, upd_ms = main_leg['dt'], main_leg['upd_ms']
     env_steps = G * N * T * args.steps  # every rank's tasks (the max-over-ranks time covers them all)
     value = env_steps / dt
-    # the fixed population split over the ranks (pop 40 -> 40 / 20 / 10 / 5 per GPU), measured in the
-    # same run: the strong-scaling curve the north star targets (>= 6x at 1 -> 8), beside the weak headline
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, main_leg.pop('outputs'), rank)
+    # --full: the fixed population split over the ranks (pop 40 -> 40 / 20 / 10 / 5 per GPU), measured in
+    # the same run: the strong-scaling curve the north star targets (>= 6x at 1 -> 8), beside the weak headline
     strong = None
-    if not args.no_strong and args.scaling == 'weak' and world > 1:
+    if args.full and not args.no_strong and args.scaling == 'weak' and world > 1:
         sblocks = [task_block(args.strong_tasks, r, world) for r in range(world)]
         sl = main_leg if sblocks == blocks else leg(args, spec, dev, rank, world, sblocks, 'strong')
         strong = {'global_tasks': args.strong_tasks, 'tasks_per_rank': [b - a for a, b in sblocks],
@@ -676,8 +725,11 @@ def main():
     upd_flop = P * T * N * E * 6 * mf          # fwd (2 M_f) + bwd (4 M_f) per row per epoch, one launch
     achieved = upd_flop / (upd_ms * 1e-3) / 1e12 if upd_ms > 0 else 0.0
     kernel = main_leg['kernel']
-    traffic, traffic_src = pmc_traffic(args, f'{args.env_name}/P{P}/N{N}/T{T}/E{E}/M{M}', kernel)
-    sq, sq_why = sq_evidence(f'{args.env_name}/P{P}/N{N}/T{T}/E{E}/M{M}', kernel)
+    if args.full:  # the committed PMC / SQ summaries of this launch, quoted beside the measured rate
+        traffic, traffic_src = pmc_traffic(args, f'{args.env_name}/P{P}/N{N}/T{T}/E{E}/M{M}', kernel)
+        sq, sq_why = sq_evidence(f'{args.env_name}/P{P}/N{N}/T{T}/E{E}/M{M}', kernel)
+    else:
+        traffic, traffic_src, sq, sq_why = None, 'not quoted (--full)', None, 'not quoted (--full)'
     alg_bytes = P * T * N * E * 4 * (spec['obs_dim'] + spec['act_dim'] + 2 * spec['obj_num'] + 2)
     out = {
         'metric': METRIC, 'value': value, 'unit': 'env steps/sec', 'n_gpus': n_gpus, 'steps': args.steps,
@@ -716,10 +768,10 @@ def main():
     if args.whole_run is None:
         args.whole_run = world == 1 and args.env_name == 'MO-Walker2d-v2' and args.scaling == 'weak' \
             and not args.stub_cpu
-    if args.whole_run:
+    if args.full and args.whole_run:
         torch.cuda.empty_cache()
         out['whole_run'] = whole_run(args, value)
-    if rank == 0 and world == 1 and not args.no_cpu_baseline and not args.stub_cpu:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline and not args.stub_cpu:
         out['cpu_baseline'] = cb = cpu_baseline(args, spec, G)
         out['vs_96vcpu_extrapolated'] = value / cb['extrapolated_96vcpu']
     if rank == 0:

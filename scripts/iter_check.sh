@@ -8,7 +8,7 @@ OUT=$(pwd)/gpurun_out
 mkdir -p $OUT
 timeout -k 10 600 python -u -m pytest tests -m gpu -x -q -k "$K" --timeout 300 --timeout-method thread -p no:cacheprovider > $OUT/it_tests_$TAG.log 2>&1 || { echo TESTS FAILED; grep -E "(FAILED|ERROR|Error)" $OUT/it_tests_$TAG.log | head -20; tail -30 $OUT/it_tests_$TAG.log; exit 1; }
 tail -1 $OUT/it_tests_$TAG.log
-timeout -k 10 300 python -u bench.py --no-cpu-baseline --steps 10 --warmup 2 ${BENCH_ARGS} > $OUT/it_bench_$TAG.json 2> $OUT/it_bench_$TAG.err || { echo BENCH FAILED; tail -20 $OUT/it_bench_$TAG.err; exit 1; }
+timeout -k 10 300 python -u bench.py --full --no-cpu-baseline --steps 10 --warmup 2 ${BENCH_ARGS} > $OUT/it_bench_$TAG.json 2> $OUT/it_bench_$TAG.err || { echo BENCH FAILED; tail -20 $OUT/it_bench_$TAG.err; exit 1; }
 python -c "
 import json; d=json.load(open('$OUT/it_bench_$TAG.json')); r=d['roofline']; w=d.get('whole_run') or {}
 print('bench', round(d['value']/1e6,2), 'M/s', round(d['ms_per_step'],3), 'ms/step', r['kernel'], round(r['avg_launch_ms'],3), 'ms frac', round(r['frac'],4))

@@ -1,5 +1,5 @@
 #!/bin/bash
-# GPU box routine: the -m gpu parity suite, smoke(), the default bench line (iteration bench + whole run +
+# Routine check on the MI355X: the -m gpu parity suite, smoke(), the --full bench line (iteration bench + whole run +
 # cpu_baseline), and rocprofv3 kernel stats of the iteration bench.  libpgm.so is prebuilt in-tree.
 # Usage: bash scripts/round_check.sh TAG [--no-tests] [bench args]
 set -o pipefail
@@ -16,7 +16,7 @@ if [ $TESTS = 1 ]; then
   timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke()" > $OUT/smoke_$TAG.log 2>&1 || { echo SMOKE FAILED; tail -20 $OUT/smoke_$TAG.log; exit 1; }
   echo smoke ok
 fi
-timeout -k 10 600 python -u bench.py "$@" > $OUT/bench_$TAG.json 2> $OUT/bench_$TAG.err || { echo BENCH FAILED; tail -20 $OUT/bench_$TAG.err; exit 1; }
+timeout -k 10 600 python -u bench.py --full "$@" > $OUT/bench_$TAG.json 2> $OUT/bench_$TAG.err || { echo BENCH FAILED; tail -20 $OUT/bench_$TAG.err; exit 1; }
 python -c "
 import json; d=json.load(open('$OUT/bench_$TAG.json')); r=d['roofline']; w=d.get('whole_run') or {}; c=d.get('cpu_baseline') or {}
 print('bench', round(d['value']/1e6,2), 'M/s', round(d['ms_per_step'],3), 'ms/step', r['kernel'], round(r['avg_launch_ms'],3), 'ms frac', round(r['frac'],4))

@@ -27,7 +27,7 @@ def _line(r):
 
 
 def test_gpus2_spawns_two_ranks():
-    r = _run([sys.executable, BENCH, '--gpus', '2', '--stub-cpu', '--steps', '2', '--warmup', '1'])
+    r = _run([sys.executable, BENCH, '--gpus', '2', '--stub-cpu', '--full', '--steps', '2', '--warmup', '1'])
     assert r.returncode == 0, r.stderr[-2000:]
     d = _line(r)
     assert d['n_gpus'] == 2 and d['scaling'] == 'weak'
@@ -38,8 +38,37 @@ def test_gpus2_spawns_two_ranks():
     assert 'STUB' in d['data']
 
 
+def test_plain_run_is_lean_and_dumps_outputs(tmp_path):
+    """Without --full the line carries the headline figure only (no strong leg, whole run, CPU baseline or quoted
+    comparisons), --steps sets the timed steps behind ms_per_step, and --dump-outputs writes the last timed step's
+    objective vectors (the stub's: task index + iteration index) -- the same arrays in every run."""
+    import numpy as np
+    r = _run([sys.executable, BENCH, '--gpus', '2', '--stub-cpu', '--steps', '3', '--warmup', '1', '--tasks', '4',
+              '--dump-outputs', str(tmp_path / 'out')])
+    assert r.returncode == 0, r.stderr[-2000:]
+    d = _line(r)
+    assert d['n_gpus'] == 2 and d['steps'] == 3 and d['warmup'] == 1
+    for k in ('strong', 'whole_run', 'cpu_baseline', 'vs_96vcpu_extrapolated'):
+        assert k not in d, k
+    assert d['roofline']['traffic'] is None and d['roofline']['limiter'] is None
+    # 8 tasks x N x T env-steps per step: value and ms_per_step describe the same 3 timed steps
+    per_step = 8 * d['config']['num_processes'] * d['config']['num_steps']
+    assert d['ms_per_step'] >= 0.1 * 4 and abs(d['value'] * d['ms_per_step'] * 1e-3 / per_step - 1) < 1e-9
+    for name in ('objs.npy', 'objs_rank1.npy'):
+        objs = np.load(tmp_path / 'out' / name)
+        assert objs.dtype == np.float64 and objs.shape == (8, 2)
+        assert np.array_equal(objs, np.arange(8.0)[:, None] + 3 + np.zeros((1, 2)))  # last step: j = 1 + 3 - 1
+
+
+def test_secondary_options_need_full():
+    r = _run([sys.executable, BENCH, '--stub-cpu', '--whole-run'])
+    assert r.returncode != 0 and '--full' in r.stderr
+    assert not [l for l in r.stdout.splitlines() if l.startswith('{')]
+
+
 def test_gpus3_strong_blocks():
-    r = _run([sys.executable, BENCH, '--gpus', '3', '--stub-cpu', '--steps', '1', '--warmup', '0', '--tasks', '4'])
+    r = _run([sys.executable, BENCH, '--gpus', '3', '--stub-cpu', '--full', '--steps', '1', '--warmup', '0',
+              '--tasks', '4'])
     assert r.returncode == 0, r.stderr[-2000:]
     d = _line(r)
     assert d['n_gpus'] == 3 and d['config']['global_tasks'] == 12
@@ -53,7 +82,7 @@ def test_torchrun_matching_gpus():
         port = s.getsockname()[1]
     r = _run([sys.executable, '-m', 'torch.distributed.run', '--nnodes=1', '--nproc-per-node', '2',
               '--master-addr', '127.0.0.1', '--master-port', str(port), BENCH, '--gpus', '2', '--stub-cpu',
-              '--steps', '1', '--warmup', '1'])
+              '--full', '--steps', '1', '--warmup', '1'])
     assert r.returncode == 0, r.stderr[-2000:]
     d = _line(r)
     assert d['n_gpus'] == 2 and d['strong']['tasks_per_rank'] == [20, 20]

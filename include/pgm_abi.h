@@ -53,7 +53,7 @@
 extern "C" {
 #endif
 
-#define PGM_ABI_VERSION 4
+#define PGM_ABI_VERSION 5
 
 #define PGM_OK 0
 #define PGM_E_INVALID_ARG (-1)
@@ -77,10 +77,36 @@ extern "C" {
 #define PGM_P_LOGSTD 12    /* dist.logstd._bias       [A] (reference shape [A][1]) */
 #define PGM_NUM_PARAM_TENSORS 13
 
+/* LayerNorm towers (pgm_dims.LN = 1; model.py:201-256 with layernorm=True): every tower layer is
+ * Linear(bias=False) -> LayerNorm(H, elementwise_affine) -> tanh, so each layer carries a weight, the LayerNorm
+ * scale (gamma) and the LayerNorm shift (beta).  named_parameters() order; offsets from pgm_param_layout_ln. */
+#define PGM_PL_ACTOR_W1 0    /* base.actor.0.weight^T   [O][H] */
+#define PGM_PL_ACTOR_G1 1    /* base.actor.1.weight     [H]    */
+#define PGM_PL_ACTOR_BE1 2   /* base.actor.1.bias       [H]    */
+#define PGM_PL_ACTOR_W2 3    /* base.actor.3.weight^T   [H][H] */
+#define PGM_PL_ACTOR_G2 4    /* base.actor.4.weight     [H]    */
+#define PGM_PL_ACTOR_BE2 5   /* base.actor.4.bias       [H]    */
+#define PGM_PL_CRITIC_W1 6   /* base.critic.0.weight^T  [O][H] */
+#define PGM_PL_CRITIC_G1 7
+#define PGM_PL_CRITIC_BE1 8
+#define PGM_PL_CRITIC_W2 9   /* base.critic.3.weight^T  [H][H] */
+#define PGM_PL_CRITIC_G2 10
+#define PGM_PL_CRITIC_BE2 11
+#define PGM_PL_VALUE_W 12    /* base.critic_linear.weight^T [H][K] */
+#define PGM_PL_VALUE_B 13
+#define PGM_PL_MEAN_W 14     /* dist.fc_mean.weight^T   [H][A] */
+#define PGM_PL_MEAN_B 15
+#define PGM_PL_LOGSTD 16     /* dist.logstd._bias       [A] */
+#define PGM_NUM_PARAM_TENSORS_LN 17
+
 typedef void* pgm_stream_t; /* a hipStream_t (0 = the null stream) */
 
+/* LN (ABI 5): 0 = plain tanh towers, 1 = LayerNorm towers (params / Adam vectors in the pgm_param_layout_ln layout).
+ * LN = 1 is built for obs_dim <= 32 (17/6/2, 11/3/2, 11/3/3, 27/8/2, 8/2/2); with 376/17/2 every entry point that
+ * touches the policy returns PGM_E_UNSUPPORTED.  pgm_launch_opts is ignored for LN = 1 (one kernel family). */
 typedef struct pgm_dims {
     int32_t P, N, T, O, A, K, H;
+    int32_t LN;
 } pgm_dims;
 
 typedef struct pgm_env_spec { /* device pointers, fp64 */
@@ -159,6 +185,9 @@ const char* pgm_last_error(void);
 /* Flat per-task parameter layout: offsets[PGM_NUM_PARAM_TENSORS] (floats) and the padded
  * per-task length *total (a multiple of 64 floats). */
 int pgm_param_layout(int32_t O, int32_t A, int32_t K, int32_t H, int32_t* offsets, int32_t* total);
+/* The same for LayerNorm towers: offsets[PGM_NUM_PARAM_TENSORS_LN] in PGM_PL_* order, every tensor 16-byte aligned,
+ * *total a multiple of 64 floats. */
+int pgm_param_layout_ln(int32_t O, int32_t A, int32_t K, int32_t H, int32_t* offsets, int32_t* total);
 
 /* Policy.act on obs [P][N][O] (model.py:57-69).  noise [N][A] (shared by tasks) gives
  * action = noise*exp(logstd) + mean; deterministic=1 gives action = mean (noise ignored).
@@ -213,7 +242,9 @@ int pgm_adv_normalize(const pgm_dims* d, const pgm_rollout_buf* rb, const double
  * GPUs).  opts->update_split caps the row split; opts->update_kernel = PGM_UPDATE_FS forces the feature-split
  * update wherever it fits, PGM_UPDATE_ROWSPLIT the row-split kernels.
  * After the call, the 8-byte word at index 2P of the workspace is nonzero iff an exchange timed out
- * (the workgroups were not co-resident); the results of such a call are invalid. */
+ * (the workgroups were not co-resident); the results of such a call are invalid.
+ * d->LN = 1: ppo_update_ln_kernel, one workgroup per tower with the tower's parameters and Adam moments LDS-resident,
+ * the same norm granules and timeout word; needs 2P <= CU count (PGM_E_UNSUPPORTED otherwise); opts ignored. */
 int pgm_ppo_update(const pgm_dims* d, const pgm_ppo_hparams* hp, float* params, float* adam_m,
                    float* adam_v, int32_t* adam_step, const float* lr, const int32_t* perms,
                    const pgm_rollout_buf* rb, float* stats, void* workspace, const pgm_launch_opts* opts,

@@ -14,10 +14,14 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get('PGM_LIB') or os.path.join(HERE, 'libpgm.so')
 TEST_LIB_PATH = os.path.join(HERE, 'libpgm_test.so')  # -DPGM_TEST_HOOKS build (pgmorl_amd/build.py), tests only
 
-PGM_ABI_VERSION = 4
+PGM_ABI_VERSION = 5
 PGM_OK, PGM_E_INVALID_ARG, PGM_E_SHAPE, PGM_E_HIP, PGM_E_UNSUPPORTED = 0, -1, -2, -3, -4
 PARAM_TENSORS = ['actor_w1', 'actor_b1', 'actor_w2', 'actor_b2', 'critic_w1', 'critic_b1', 'critic_w2',
                  'critic_b2', 'value_w', 'value_b', 'mean_w', 'mean_b', 'logstd']
+# LayerNorm towers (Dims.LN = 1): PGM_PL_* order of pgm_param_layout_ln
+PARAM_TENSORS_LN = ['actor_w1', 'actor_g1', 'actor_be1', 'actor_w2', 'actor_g2', 'actor_be2',
+                    'critic_w1', 'critic_g1', 'critic_be1', 'critic_w2', 'critic_g2', 'critic_be2',
+                    'value_w', 'value_b', 'mean_w', 'mean_b', 'logstd']
 
 P_ = C.c_void_p
 I32 = C.c_int32
@@ -26,7 +30,8 @@ F64 = C.c_double
 
 
 class Dims(C.Structure):
-    _fields_ = [(n, I32) for n in ('P', 'N', 'T', 'O', 'A', 'K', 'H')]
+    """pgm_dims; LN = 1 selects the LayerNorm towers (0, the default, the plain ones)."""
+    _fields_ = [(n, I32) for n in ('P', 'N', 'T', 'O', 'A', 'K', 'H', 'LN')]
 
 
 class EnvSpec(C.Structure):
@@ -86,6 +91,7 @@ _SIGS = {
     'pgm_abi_version': (C.c_int, []),
     'pgm_last_error': (C.c_char_p, []),
     'pgm_param_layout': (C.c_int, [I32, I32, I32, I32, C.POINTER(I32), C.POINTER(I32)]),
+    'pgm_param_layout_ln': (C.c_int, [I32, I32, I32, I32, C.POINTER(I32), C.POINTER(I32)]),
     'pgm_act_forward': (C.c_int, [C.POINTER(Dims), P_, P_, P_, I32, P_, P_, P_, P_]),
     'pgm_env_reset': (C.c_int, [C.POINTER(Dims), C.POINTER(EnvSpec), C.POINTER(EnvState), C.POINTER(NormState),
                                 P_, P_]),
@@ -161,3 +167,11 @@ def param_layout(O, A, K, H=64):
     tot = I32()
     check(lib().pgm_param_layout(O, A, K, H, offs, C.byref(tot)), 'pgm_param_layout')
     return dict(zip(PARAM_TENSORS, list(offs))), tot.value
+
+
+def param_layout_ln(O, A, K, H=64):
+    """(offsets dict, total) of the flat per-task parameter vector of LayerNorm towers (pgm_param_layout_ln)."""
+    offs = (I32 * len(PARAM_TENSORS_LN))()
+    tot = I32()
+    check(lib().pgm_param_layout_ln(O, A, K, H, offs, C.byref(tot)), 'pgm_param_layout_ln')
+    return dict(zip(PARAM_TENSORS_LN, list(offs))), tot.value

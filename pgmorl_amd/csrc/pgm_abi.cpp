@@ -104,6 +104,23 @@ Layout make_layout(int O, int A, int K, int Hd) {
     return L;
 }
 
+LayoutLN make_layout_ln(int O, int A, int K, int Hd) {
+    const int32_t sizes[PGM_NUM_PARAM_TENSORS_LN] = {
+        O * Hd, Hd, Hd, Hd * Hd, Hd, Hd,   // actor tower: W1, gamma1, beta1, W2, gamma2, beta2
+        O * Hd, Hd, Hd, Hd * Hd, Hd, Hd,   // critic tower
+        Hd * K, K,                         // critic_linear
+        Hd * A, A,                         // fc_mean
+        A};                                // logstd
+    LayoutLN L;
+    int32_t p = 0;
+    for (int i = 0; i < PGM_NUM_PARAM_TENSORS_LN; ++i) {
+        L.off[i] = p;
+        p = round_up(p + sizes[i], 4);  // 16-byte aligned tensors
+    }
+    L.total = round_up(p, 64);
+    return L;
+}
+
 }  // namespace pgm
 
 extern "C" {
@@ -119,6 +136,17 @@ int pgm_param_layout(int32_t O, int32_t A, int32_t K, int32_t H, int32_t* offset
     }
     pgm::Layout L = pgm::make_layout(O, A, K, H);
     for (int i = 0; i < PGM_NUM_PARAM_TENSORS; ++i) offsets[i] = L.off[i];
+    *total = L.total;
+    return PGM_OK;
+}
+
+int pgm_param_layout_ln(int32_t O, int32_t A, int32_t K, int32_t H, int32_t* offsets, int32_t* total) {
+    if (O <= 0 || A <= 0 || K <= 0 || H <= 0 || !offsets || !total) {
+        pgm::set_error("pgm_param_layout_ln: bad arguments");
+        return PGM_E_INVALID_ARG;
+    }
+    pgm::LayoutLN L = pgm::make_layout_ln(O, A, K, H);
+    for (int i = 0; i < PGM_NUM_PARAM_TENSORS_LN; ++i) offsets[i] = L.off[i];
     *total = L.total;
     return PGM_OK;
 }

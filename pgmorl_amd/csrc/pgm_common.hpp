@@ -21,6 +21,12 @@ struct Layout {
     int32_t total;
 };
 Layout make_layout(int O, int A, int K, int Hd);
+// LayerNorm towers (pgm_dims.LN = 1): the 17 tensors of pgm_param_layout_ln
+struct LayoutLN {
+    int32_t off[PGM_NUM_PARAM_TENSORS_LN];
+    int32_t total;
+};
+LayoutLN make_layout_ln(int O, int A, int K, int Hd);
 // pgm_ppo_update workspace: [2 PGM_NS_MAX P + 1] tagged 8-byte granules (tower-norm hand-offs of every
 // (task, tower, row part); word 2P = timeout flag), padded to 256 bytes; the gradient exchange of the
 // row-split updates, [P][2 towers][PGM_NS_MAX row parts][2 parities] slots of (tower image + 1) granules; then

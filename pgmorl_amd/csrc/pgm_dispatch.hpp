@@ -44,4 +44,19 @@ inline int check_dims(const pgm_dims* d, const char* what) {
     return PGM_OK;
 }
 
+// pgm_dims.LN of the entry points that touch the policy: 0 or 1, and LayerNorm towers only where layer 1 is
+// LDS-resident (obs_dim <= 32; Humanoid's streamed layer 1 has no LayerNorm kernel)
+inline int check_ln(const pgm_dims* d, const char* what) {
+    if (d->LN != 0 && d->LN != 1) {
+        set_error("%s: pgm_dims.LN = %d (0 plain towers, 1 LayerNorm towers)", what, d->LN);
+        return PGM_E_INVALID_ARG;
+    }
+    if (d->LN == 1 && d->O > 32) {
+        set_error("%s: LayerNorm towers are built for obs_dim <= 32 (17/6/2, 11/3/2, 11/3/3, 27/8/2, 8/2/2); obs_dim %d "
+                  "(MO-Humanoid) needs a streamed layer-1 LayerNorm kernel that does not exist", what, d->O);
+        return PGM_E_UNSUPPORTED;
+    }
+    return PGM_OK;
+}
+
 }  // namespace pgm

@@ -659,6 +659,284 @@ __global__ __launch_bounds__(RT) void eval_kernel(EvalArgs a) {
 }
 
 // ------------------------------------------------------------------------------------------
+// LayerNorm towers (pgm_dims.LN = 1; model.py:201-256 with layernorm=True): Linear(bias=False) -> LayerNorm(64) ->
+// tanh, twice per tower.  One wave per (env row, tower) with a lane per hidden unit, as policy_forward: the 64
+// pre-activations of a row sit in one wave, so the LayerNorm mean and the variance of the mean-subtracted values are
+// 64-lane DPP sums (wave_sum64, no LDS round trip).  Env step, VecNormalize, insert bookkeeping and the counter RNG
+// are the device functions above, unchanged; the kernels below are the plain ones with this forward.
+template <int O, int A, int K>
+struct PolRegLN {
+    float w1[O];
+    float w2[H];
+    float wh[A > K ? A : K];
+    float g1, be1, g2, be2;
+};
+
+template <int O, int A, int K>
+__device__ void load_policy_ln(PolSmem<O, A, K>& S, const float* __restrict__ prm, const LayoutLN& L) {
+    const int t = threadIdx.x;
+    if (t < K) S.bv[t] = prm[L.off[PGM_PL_VALUE_B] + t];
+    if (t < A) {
+        S.bm[t] = prm[L.off[PGM_PL_MEAN_B] + t];
+        S.logstd[t] = prm[L.off[PGM_PL_LOGSTD] + t];
+    }
+}
+
+template <int O, int A, int K>
+__device__ void load_polreg_ln(PolRegLN<O, A, K>& R, const float* __restrict__ prm, const LayoutLN& L) {
+    const int t = threadIdx.x, lane = t & 63, m = (t >> 6) & 1;  // m: 0 critic, 1 actor
+    const int b = m == 0 ? PGM_PL_CRITIC_W1 : PGM_PL_ACTOR_W1;   // the tower's six tensors are consecutive
+#pragma unroll
+    for (int k = 0; k < O; ++k) R.w1[k] = prm[L.off[b] + k * H + lane];
+#pragma unroll
+    for (int k = 0; k < H; ++k) R.w2[k] = prm[L.off[b + 3] + k * H + lane];
+    constexpr int NQ = A > K ? A : K;
+#pragma unroll
+    for (int q = 0; q < NQ; ++q)
+        R.wh[q] = m == 0 ? (q < K ? prm[L.off[PGM_PL_VALUE_W] + lane * K + q] : 0.f)
+                         : (q < A ? prm[L.off[PGM_PL_MEAN_W] + lane * A + q] : 0.f);
+    R.g1 = prm[L.off[b + 1] + lane];
+    R.be1 = prm[L.off[b + 2] + lane];
+    R.g2 = prm[L.off[b + 4] + lane];
+    R.be2 = prm[L.off[b + 5] + lane];
+}
+
+// 1 / sqrt(x) in fp32: hardware estimate + one Newton step (<= 1 ulp)
+__device__ __forceinline__ float rsqrt_nr(float x) {
+    const float r = __builtin_amdgcn_rsqf(x);
+    return r * fmaf(-0.5f * x * r, r, 1.5f);
+}
+// LayerNorm over the wave's 64 lanes + affine + tanh: the variance is the mean of the mean-subtracted squares
+// (E[z^2] - mean^2 cancels in fp32)
+__device__ __forceinline__ float ln_tanh64(float z, float g, float be) {
+    const float mu = wave_sum64(z) * (1.f / 64.f);
+    const float dz = z - mu;
+    const float var = wave_sum64(dz * dz) * (1.f / 64.f);
+    return tanh_f(fmaf(dz * rsqrt_nr(var + 1e-5f), g, be));
+}
+
+// policy_forward with LayerNorm towers: same wave / row split, same outputs (S.val, S.mu), one barrier at the end
+template <int O, int A, int K>
+__device__ void policy_forward_ln(PolSmem<O, A, K>& S, const PolRegLN<O, A, K>& R, int N) {
+    const int t = threadIdx.x, lane = t & 63, w = t >> 6, m = w & 1, rg = w >> 1, c = m * H + lane;
+    constexpr int RPT = NMAX / 2;
+#pragma unroll
+    for (int i = 0; i < RPT; ++i) {  // tower layer 1
+        const int r = rg + 2 * i;
+        if (r < N) {
+            float acc = 0.f;
+#pragma unroll
+            for (int k = 0; k < opad<O>(); k += 4) {
+                const float4 x = *reinterpret_cast<const float4*>(&S.x[r][k]);
+                acc = fmaf(x.x, R.w1[k], acc);
+                if (k + 1 < O) acc = fmaf(x.y, R.w1[k + 1], acc);
+                if (k + 2 < O) acc = fmaf(x.z, R.w1[k + 2], acc);
+                if (k + 3 < O) acc = fmaf(x.w, R.w1[k + 3], acc);
+            }
+            S.h1[r][c] = ln_tanh64(acc, R.g1, R.be1);
+        }
+    }
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // h1 row visible to this wave (lockstep)
+    __builtin_amdgcn_wave_barrier();
+#pragma unroll
+    for (int i = 0; i < RPT; ++i) {  // tower layer 2 + heads
+        const int r = rg + 2 * i;
+        if (r < N) {
+            float a0 = 0.f, a1 = 0.f, a2 = 0.f, a3 = 0.f;
+#pragma unroll
+            for (int k = 0; k < H; k += 4) {
+                const float4 h = *reinterpret_cast<const float4*>(&S.h1[r][m * H + k]);
+                a0 = fmaf(h.x, R.w2[k], a0);
+                a1 = fmaf(h.y, R.w2[k + 1], a1);
+                a2 = fmaf(h.z, R.w2[k + 2], a2);
+                a3 = fmaf(h.w, R.w2[k + 3], a3);
+            }
+            const float h2 = ln_tanh64((a0 + a1) + (a2 + a3), R.g2, R.be2);
+            if (m == 0) {
+#pragma unroll
+                for (int q = 0; q < K; ++q) {
+                    const float v = wave_sum64(h2 * R.wh[q]);
+                    if (lane == 0) S.val[r][q] = v + S.bv[q];
+                }
+            } else {
+#pragma unroll
+                for (int q = 0; q < A; ++q) {
+                    const float v = wave_sum64(h2 * R.wh[q]);
+                    if (lane == 0) S.mu[r][q] = v + S.bm[q];
+                }
+            }
+        }
+    }
+    lds_sync();
+}
+
+template <int O, int A, int K>
+__global__ __launch_bounds__(RT) void act_forward_ln_kernel(ActArgs a, LayoutLN L) {
+    extern __shared__ __attribute__((aligned(16))) char smem_raw[];
+    auto& S = *reinterpret_cast<PolSmem<O, A, K>*>(smem_raw);
+    const int p = blockIdx.x, t = threadIdx.x, N = a.N;
+    const float* prm = a.params + (size_t)p * L.total;
+    PolRegLN<O, A, K> R;
+    load_policy_ln(S, prm, L);
+    load_polreg_ln(R, prm, L);
+    for (int i = t; i < N * opad<O>(); i += RT) {  // rows zero-padded to the float4 reads of layer 1
+        const int n = i / opad<O>(), o = i % opad<O>();
+        S.x[n][o] = o < O ? a.obs[((size_t)p * N + n) * O + o] : 0.f;
+    }
+    __syncthreads();
+    policy_forward_ln(S, R, N);
+    for (int i = t; i < N * K; i += RT) a.value[(size_t)p * N * K + i] = S.val[i / K][i % K];
+    for (int i = t; i < N * A; i += RT) {
+        const int n = i / A, j = i % A;
+        const float mu = S.mu[n][j], ls = S.logstd[j], sd = expf(ls);
+        const float act = a.deterministic ? mu : fmaf(a.noise[i], sd, mu);
+        const float dz = (act - mu) / sd;
+        S.lp[n][j] = -0.5f * dz * dz - ls - LOG_SQRT_2PI;
+        a.action[(size_t)p * N * A + i] = act;
+    }
+    __syncthreads();
+    if (t < N) {
+        float s = 0.f;
+        for (int j = 0; j < A; ++j) s += S.lp[t][j];
+        a.logp[(size_t)p * N + t] = s;
+    }
+}
+
+template <int O, int A, int K>
+__global__ __launch_bounds__(RT) void rollout_ln_kernel(RolloutArgs a, LayoutLN L) {
+    extern __shared__ __attribute__((aligned(16))) char smem_raw[];
+    auto& S = *reinterpret_cast<StepSmem<O, A, K>*>(smem_raw);
+    auto& P = S.pol;
+    auto& E = S.env;
+    const int p = blockIdx.x, t = threadIdx.x, N = a.N, T = a.T;
+    const NormCfg nc = norm_cfg(a.ns);
+    const Spec<O, A, K> sp{E, a.spec, a.st.s0};
+    const float* prm = a.params + (size_t)p * L.total;
+    float* obs = a.rb.obs + (size_t)p * (T + 1) * N * O;
+    float* act = a.rb.actions + (size_t)p * T * N * A;
+    float* logp = a.rb.logp + (size_t)p * T * N;
+    float* val = a.rb.values + (size_t)p * (T + 1) * N * K;
+    float* rew = a.rb.rewards + (size_t)p * T * N * K;
+    float* masks = a.rb.masks + (size_t)p * (T + 1) * N;
+    float* bad = a.rb.bad_masks + (size_t)p * (T + 1) * N;
+
+    PolRegLN<O, A, K> R;
+    load_policy_ln(P, prm, L);
+    load_polreg_ln(R, prm, L);
+    load_spec(E, a.spec, a.st.s0, N);
+    load_env(E, a.st, a.ns, p, N);
+    if (a.carry) {  // after_update(): slot T -> slot 0 (storage.py:71-75); each thread re-reads its own writes
+        for (int i = t; i < N * O; i += RT) obs[i] = obs[(size_t)T * N * O + i];
+        if (t < N) {
+            masks[t] = masks[(size_t)T * N + t];
+            bad[t] = bad[(size_t)T * N + t];
+        }
+    }
+    for (int i = t; i < NMAX * opad<O>(); i += RT) (&P.x[0][0])[i] = 0.f;  // the float4 pad columns stay zero
+    __syncthreads();
+    for (int i = t; i < N * O; i += RT) P.x[i / O][i % O] = obs[i];
+    __syncthreads();
+
+    // the lane drawing (n, a) of each step keeps its noise one step ahead in a register
+    const bool drawer = t < N * A;
+    float eps_next = 0.f;
+    if (drawer) eps_next = a.noise ? a.noise[t] : counter_normal(a.seed, (uint64_t)t);
+    for (int step = 0; step < T; ++step) {
+        const float eps = eps_next;
+        if (drawer && step + 1 < T) {
+            const size_t idx = (size_t)(step + 1) * N * A + t;
+            eps_next = a.noise ? a.noise[idx] : counter_normal(a.seed, idx);
+        }
+        policy_forward_ln(P, R, N);
+        for (int i = t; i < N * K; i += RT) val[(size_t)step * N * K + i] = P.val[i / K][i % K];
+        sample_actions(P, E, sp, N, eps, act + (size_t)step * N * A);
+        if (t < N) {
+            float s = 0.f;
+            for (int j = 0; j < A; ++j) s += P.lp[t][j];
+            logp[(size_t)step * N + t] = s;
+        }
+        env_dynamics(E, sp, N, a.spec.max_episode_steps);
+        vecnorm_stats(E, sp, N, nc);
+        vecnorm_emit<O, A, K, opad<O>()>(E, N, nc, P.x, obs + (size_t)(step + 1) * N * O,
+                                         rew + (size_t)step * N * K, masks + (size_t)(step + 1) * N,
+                                         bad + (size_t)(step + 1) * N);
+    }
+    // bootstrap value (mopg.py:132-135) -> value_preds[T] (storage.py:85)
+    policy_forward_ln(P, R, N);
+    for (int i = t; i < N * K; i += RT) val[(size_t)T * N * K + i] = P.val[i / K][i % K];
+    __syncthreads();
+    store_env(E, a.st, a.ns, p, N);
+}
+
+template <int O, int A, int K>
+__global__ __launch_bounds__(RT) void eval_ln_kernel(EvalArgs a, LayoutLN L) {
+    extern __shared__ __attribute__((aligned(16))) char smem_raw[];
+    auto& S = *reinterpret_cast<StepSmem<O, A, K>*>(smem_raw);
+    auto& P = S.pol;
+    auto& E = S.env;
+    const int p = blockIdx.x, t = threadIdx.x;
+    const float* prm = a.params + (size_t)p * L.total;
+    PolRegLN<O, A, K> R;
+    load_policy_ln(P, prm, L);
+    load_polreg_ln(R, prm, L);
+    load_spec(E, a.spec, a.s0_eval, 1);
+    for (int o = t; o < O; o += RT) {  // mopg.py:37-38: fp64 normalisation with fixed eps/clip
+        E.ob_mean[o] = a.use_ob ? a.ob_mean[(size_t)p * O + o] : 0.0;
+        E.ob_inv[o] = a.use_ob ? 1.0 / sqrt(a.ob_var[(size_t)p * O + o] + 1e-8) : 1.0;
+    }
+    if (t < opad<O>()) P.x[0][t] = 0.f;
+    if (t < K) E.objsum[t] = 0.0;
+    __syncthreads();
+    for (int e = 0; e < a.eval_num; ++e) {
+        const double* s0 = a.s0_eval + (size_t)e * O;
+        const Spec<O, A, K> sp{E, a.spec, s0};
+        for (int o = t; o < O; o += RT) E.s[0][o] = s0[o];
+        if (t == 0) E.elapsed[0] = 0;
+        double g = 1.0;
+        __syncthreads();
+        while (true) {
+            for (int o = t; o < O; o += RT) {  // obs is NOT rounded through fp32 before normalising
+                double v = E.s[0][o];
+                if (a.use_ob) v = clipd((v - E.ob_mean[o]) * E.ob_inv[o], -10.0, 10.0);
+                P.x[0][o] = (float)v;
+            }
+            lds_sync();
+            policy_forward_ln(P, R, 1);
+            if (t < A) E.ac[0][t] = clipd((double)P.mu[0][t], sp.lo(t), sp.hi(t));
+            lds_sync();
+            env_dynamics(E, sp, 1, a.spec.max_episode_steps);
+            if (t < K) E.objsum[t] += g * E.objraw[0][t];
+            if (!a.raw) g *= a.gamma;
+            const int done = E.done[0];
+            for (int o = t; o < O; o += RT) E.s[0][o] = E.snew[0][o];
+            lds_sync();
+            if (done) break;
+        }
+    }
+    if (t < K) a.objs[(size_t)p * K + t] = E.objsum[t] / (double)a.eval_num;
+}
+
+// ------------------------------------------------------------------------------------------
+template <class Kern, class... Args>
+static int launch_smem_ln(Kern k, int grid, size_t smem, hipStream_t s, const char* what, const Args&... args) {
+    hipError_t e = hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
+    if (e != hipSuccess) return hip_fail(e, what);
+    hipLaunchKernelGGL(k, dim3(grid), dim3(RT), smem, s, args...);
+    return launch_status(what);
+}
+// f(ic<O>, ic<A>, ic<K>) for the obs_dim <= 32 dims (check_ln has refused wider observations)
+template <class F>
+static int dispatch_dims_ln(const pgm_dims* d, const char* what, F&& f) {
+    return dispatch_dims(d->O, d->A, d->K, what, [&](auto o, auto aa, auto k) -> int {
+        if constexpr (decltype(o)::value > 32) {
+            set_error("%s: LayerNorm towers need obs_dim <= 32", what);
+            return PGM_E_UNSUPPORTED;
+        } else {
+            return f(o, aa, k);
+        }
+    });
+}
+
 template <class Kern, class Args>
 static int launch_smem(Kern k, int grid, size_t smem, hipStream_t s, const Args& args, const char* what) {
     if (smem > 160 * 1024) {
@@ -692,11 +970,20 @@ extern "C" {
 int pgm_act_forward(const pgm_dims* d, const float* params, const float* obs, const float* noise,
                     int32_t deterministic, float* value, float* action, float* logp, pgm_stream_t stream) {
     if (int rc = check_dims(d, "pgm_act_forward")) return rc;
+    if (int rc = check_ln(d, "pgm_act_forward")) return rc;
     if (!params || !obs || !value || !action || !logp || (!deterministic && !noise)) {
         set_error("pgm_act_forward: null pointer (noise is required unless deterministic)");
         return PGM_E_INVALID_ARG;
     }
     ActArgs a{d->P, d->N, make_layout(d->O, d->A, d->K, d->H), params, obs, noise, deterministic, value, action, logp};
+    if (d->LN) {
+        const LayoutLN LL = make_layout_ln(d->O, d->A, d->K, d->H);
+        return dispatch_dims_ln(d, "pgm_act_forward", [&](auto o, auto aa, auto k) {
+            constexpr int O = decltype(o)::value, A = decltype(aa)::value, K = decltype(k)::value;
+            return launch_smem_ln(act_forward_ln_kernel<O, A, K>, d->P, sizeof(PolSmem<O, A, K>), (hipStream_t)stream,
+                                  "pgm_act_forward", a, LL);
+        });
+    }
     return dispatch_dims(d->O, d->A, d->K, "pgm_act_forward", [&](auto o, auto aa, auto k) {
         constexpr int O = decltype(o)::value, A = decltype(aa)::value, K = decltype(k)::value;
         return launch_smem(act_forward_kernel<O, A, K>, d->P, sizeof(PolSmem<O, A, K>), (hipStream_t)stream, a,
@@ -749,6 +1036,7 @@ int pgm_rollout(const pgm_dims* d, const float* params, const pgm_env_spec* spec
                 const pgm_norm_state* ns, const pgm_rollout_buf* rb, const float* noise, uint64_t seed,
                 int32_t carry, const pgm_launch_opts* opts, pgm_stream_t stream) {
     if (int rc = env_common(d, spec, st, ns, "pgm_rollout")) return rc;
+    if (int rc = check_ln(d, "pgm_rollout")) return rc;
     pgm_launch_opts o;
     if (int rc = read_opts(opts, &o, "pgm_rollout")) return rc;
     if (!params || !rb || !rb->obs || !rb->actions || !rb->logp || !rb->values || !rb->rewards || !rb->masks ||
@@ -762,6 +1050,14 @@ int pgm_rollout(const pgm_dims* d, const float* params, const pgm_env_spec* spec
     }
     RolloutArgs a{d->P, d->N, d->T, make_layout(d->O, d->A, d->K, d->H), params, *spec, *st, *ns, *rb,
                   noise, seed, carry};
+    if (d->LN) {  // LayerNorm towers: one kernel family, opts ignored
+        const LayoutLN LL = make_layout_ln(d->O, d->A, d->K, d->H);
+        return dispatch_dims_ln(d, "pgm_rollout", [&](auto o, auto aa, auto k) {
+            constexpr int O = decltype(o)::value, A = decltype(aa)::value, K = decltype(k)::value;
+            return launch_smem_ln(rollout_ln_kernel<O, A, K>, d->P, sizeof(StepSmem<O, A, K>), (hipStream_t)stream,
+                                  "pgm_rollout", a, LL);
+        });
+    }
     const bool block = o.rollout_kernel == 1;  // the workgroup-per-step kernel (A/B, tests)
     if (!block && rollout_lanes_supported(d)) return launch_rollout_lanes(d, a, (hipStream_t)stream);
     if (!block && rollout_wide_supported(d)) return launch_rollout_wide(d, a, (hipStream_t)stream);
@@ -776,6 +1072,7 @@ int pgm_eval(const pgm_dims* d, const float* params, const pgm_env_spec* spec, c
              const double* ob_var, const double* s0_eval, int32_t eval_num, int32_t use_ob_rms, int32_t raw,
              double gamma, double* objs_out, const pgm_launch_opts* opts, pgm_stream_t stream) {
     if (int rc = check_dims(d, "pgm_eval")) return rc;
+    if (int rc = check_ln(d, "pgm_eval")) return rc;
     pgm_launch_opts o;
     if (int rc = read_opts(opts, &o, "pgm_eval")) return rc;
     if (!params || !spec_ok(spec) || !s0_eval || !objs_out || eval_num <= 0 || (use_ob_rms && (!ob_mean || !ob_var))) {
@@ -784,6 +1081,14 @@ int pgm_eval(const pgm_dims* d, const float* params, const pgm_env_spec* spec, c
     }
     EvalArgs a{d->P, make_layout(d->O, d->A, d->K, d->H), params, *spec, ob_mean, ob_var, s0_eval,
                eval_num, use_ob_rms, raw, gamma, objs_out};
+    if (d->LN) {  // LayerNorm towers: one kernel family, opts ignored
+        const LayoutLN LL = make_layout_ln(d->O, d->A, d->K, d->H);
+        return dispatch_dims_ln(d, "pgm_eval", [&](auto o, auto aa, auto k) {
+            constexpr int O = decltype(o)::value, A = decltype(aa)::value, K = decltype(k)::value;
+            return launch_smem_ln(eval_ln_kernel<O, A, K>, d->P, sizeof(StepSmem<O, A, K>), (hipStream_t)stream,
+                                  "pgm_eval", a, LL);
+        });
+    }
     const bool block = o.eval_kernel == 1;  // the workgroup-per-step kernel (A/B, tests)
     if (!block && eval_waves_supported(d, eval_num)) return launch_eval_waves(d, a, (hipStream_t)stream);
     if (!block && eval_wide_supported(d, eval_num)) return launch_eval_wide(d, a, (hipStream_t)stream);

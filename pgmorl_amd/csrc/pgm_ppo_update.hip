@@ -521,21 +521,33 @@ int ppo_update_wide(const pgm_dims* d, const pgm_ppo_hparams* hp, float* params,
 
 using namespace pgm;
 
-extern "C" size_t pgm_ppo_update_workspace_bytes(const pgm_dims* d) { return d ? ppo_workspace_bytes(d) : 0; }
+// (LN = 1 uses the flag granules only; the size stays that of the plain layout so one rule covers both, and a
+// LayerNorm request with an unsupported obs_dim reports 0)
+extern "C" size_t pgm_ppo_update_workspace_bytes(const pgm_dims* d) {
+    if (!d || check_ln(d, "pgm_ppo_update_workspace_bytes")) return 0;
+    return ppo_workspace_bytes(d);
+}
 
 namespace pgm {
 int describe_update_mfma(const pgm_dims* d, const pgm_ppo_hparams* hp, const pgm_launch_opts& o, char* buf, int n);
 int describe_update_wide(const pgm_dims* d, const pgm_launch_opts& o, char* buf, int n);
+// LayerNorm towers (pgm_ppo_ln.hip)
+int describe_update_ln(char* buf, int n);
+int ppo_update_ln(const pgm_dims* d, const pgm_ppo_hparams* hp, float* params, float* adam_m, float* adam_v,
+                  int32_t* adam_step, const float* lr, const int32_t* perms, const pgm_rollout_buf* rb, float* stats,
+                  void* workspace, hipStream_t stream);
 }
 extern "C" int pgm_ppo_update_variant(const pgm_dims* d, const pgm_ppo_hparams* hp, const pgm_launch_opts* opts,
                                       char* buf, int n) {
     if (int rc = check_dims(d, "pgm_ppo_update_variant")) return rc;
+    if (int rc = check_ln(d, "pgm_ppo_update_variant")) return rc;
     if (!hp || !buf || n <= 0 || hp->num_mini_batch <= 0) {
         set_error("pgm_ppo_update_variant: null pointer or empty buffer");
         return PGM_E_INVALID_ARG;
     }
     pgm_launch_opts o;
     if (int rc = read_opts(opts, &o, "pgm_ppo_update_variant")) return rc;
+    if (d->LN) return describe_update_ln(buf, n) > 0 ? PGM_OK : PGM_E_INVALID_ARG;
     if (o.update_kernel == PGM_UPDATE_VALU)
         return snprintf(buf, n, "ppo_update_kernel (VALU, A/B)") > 0 ? PGM_OK : PGM_E_INVALID_ARG;
     if (d->O <= 32) return describe_update_mfma(d, hp, o, buf, n) > 0 ? PGM_OK : PGM_E_INVALID_ARG;
@@ -557,6 +569,7 @@ bool pgm::ws_take_zeroed(const void* ws, size_t need) {
 
 extern "C" int pgm_ppo_update_reset(const pgm_dims* d, void* workspace, pgm_stream_t stream) {
     if (int rc = check_dims(d, "pgm_ppo_update_reset")) return rc;
+    if (int rc = check_ln(d, "pgm_ppo_update_reset")) return rc;
     if (!workspace) {
         set_error("pgm_ppo_update_reset: null workspace");
         return PGM_E_INVALID_ARG;
@@ -574,6 +587,7 @@ extern "C" int pgm_ppo_update(const pgm_dims* d, const pgm_ppo_hparams* hp, floa
                               const pgm_rollout_buf* rb, float* stats, void* workspace, const pgm_launch_opts* opts,
                               pgm_stream_t stream) {
     if (int rc = check_dims(d, "pgm_ppo_update")) return rc;
+    if (int rc = check_ln(d, "pgm_ppo_update")) return rc;
     pgm_launch_opts o;
     if (int rc = read_opts(opts, &o, "pgm_ppo_update")) return rc;
     if (!hp || !params || !adam_m || !adam_v || !adam_step || !lr || !perms || !rb || !rb->obs || !rb->actions ||
@@ -586,6 +600,9 @@ extern "C" int pgm_ppo_update(const pgm_dims* d, const pgm_ppo_hparams* hp, floa
         set_error("pgm_ppo_update: need T*N (%d) >= num_mini_batch (%d) > 0 and ppo_epoch > 0", B, hp->num_mini_batch);
         return PGM_E_SHAPE;
     }
+    if (d->LN)  // LayerNorm towers: one kernel family, opts ignored
+        return ppo_update_ln(d, hp, params, adam_m, adam_v, adam_step, lr, perms, rb, stats, workspace,
+                             (hipStream_t)stream);
     // f32-MFMA kernels: obs_dim <= 32 (Walker, Cheetah, Hopper, Ant, Swimmer) with LDS-resident towers, wider
     // observations (Humanoid) with layer 1 in L2; the VALU kernel is kept for A/B measurements
     // (opts.update_kernel = PGM_UPDATE_VALU) and covers obs_dim <= 64

@@ -3,12 +3,13 @@
 The device stores every weight TRANSPOSED ([in][out], so a lane per output unit reads
 consecutive addresses) in the reference's named_parameters() order, each tensor 16-byte aligned
 (offsets from pgm_param_layout, include/pgm_abi.h).  State-dict keys are the reference's
-(a2c_ppo_acktr/model.py:211-254, a2c_ppo_acktr/distributions.py:78-79) for layernorm=False.
+(a2c_ppo_acktr/model.py:211-254, a2c_ppo_acktr/distributions.py:78-79): STATE_KEYS for layernorm=False,
+STATE_KEYS_LN (Linear(bias=False) -> LayerNorm -> tanh towers, 17 tensors, pgm_param_layout_ln) for layernorm=True.
 """
 import numpy as np
 import torch
 
-from ._lib import param_layout
+from ._lib import param_layout, param_layout_ln
 
 # (state_dict key, device tensor name, transposed on device)
 STATE_KEYS = [
@@ -28,7 +29,42 @@ STATE_KEYS = [
 ]
 
 
-def ref_shapes(O, A, K, H=64):
+# layernorm=True: each tower is Linear(bias=False), LayerNorm, Tanh, Linear(bias=False), LayerNorm, Tanh (modules
+# 0, 1, 3, 4 carry parameters; LayerNorm .weight is gamma, .bias is beta)
+STATE_KEYS_LN = [
+    ('base.actor.0.weight', 'actor_w1', True),
+    ('base.actor.1.weight', 'actor_g1', False),
+    ('base.actor.1.bias', 'actor_be1', False),
+    ('base.actor.3.weight', 'actor_w2', True),
+    ('base.actor.4.weight', 'actor_g2', False),
+    ('base.actor.4.bias', 'actor_be2', False),
+    ('base.critic.0.weight', 'critic_w1', True),
+    ('base.critic.1.weight', 'critic_g1', False),
+    ('base.critic.1.bias', 'critic_be1', False),
+    ('base.critic.3.weight', 'critic_w2', True),
+    ('base.critic.4.weight', 'critic_g2', False),
+    ('base.critic.4.bias', 'critic_be2', False),
+    ('base.critic_linear.weight', 'value_w', True),
+    ('base.critic_linear.bias', 'value_b', False),
+    ('dist.fc_mean.weight', 'mean_w', True),
+    ('dist.fc_mean.bias', 'mean_b', False),
+    ('dist.logstd._bias', 'logstd', False),
+]
+
+
+def state_keys(layernorm=False):
+    return STATE_KEYS_LN if layernorm else STATE_KEYS
+
+
+def ref_shapes(O, A, K, H=64, layernorm=False):
+    if layernorm:
+        sh = {}
+        for tw in ('actor', 'critic'):
+            sh.update({f'base.{tw}.0.weight': (H, O), f'base.{tw}.1.weight': (H,), f'base.{tw}.1.bias': (H,),
+                       f'base.{tw}.3.weight': (H, H), f'base.{tw}.4.weight': (H,), f'base.{tw}.4.bias': (H,)})
+        sh.update({'base.critic_linear.weight': (K, H), 'base.critic_linear.bias': (K,),
+                   'dist.fc_mean.weight': (A, H), 'dist.fc_mean.bias': (A,), 'dist.logstd._bias': (A, 1)})
+        return sh
     return {
         'base.actor.0.weight': (H, O), 'base.actor.0.bias': (H,), 'base.actor.2.weight': (H, H),
         'base.actor.2.bias': (H,), 'base.critic.0.weight': (H, O), 'base.critic.0.bias': (H,),
@@ -39,15 +75,17 @@ def ref_shapes(O, A, K, H=64):
 
 
 class ParamLayout:
-    def __init__(self, O, A, K, H=64):
+    def __init__(self, O, A, K, H=64, layernorm=False):
         self.O, self.A, self.K, self.H = O, A, K, H
-        self.offsets, self.total = param_layout(O, A, K, H)
-        self.shapes = ref_shapes(O, A, K, H)
+        self.layernorm = bool(layernorm)
+        self.keys = state_keys(self.layernorm)  # (state_dict key, device tensor, transposed), parameter order
+        self.offsets, self.total = (param_layout_ln if self.layernorm else param_layout)(O, A, K, H)
+        self.shapes = ref_shapes(O, A, K, H, self.layernorm)
 
     def flatten(self, tensors, dtype=np.float32):
         """Reference-shaped tensors (dict key -> array-like, e.g. a state_dict) -> flat [total] array."""
         out = np.zeros(self.total, dtype=dtype)
-        for key, name, tr in STATE_KEYS:
+        for key, name, tr in self.keys:
             v = tensors[key]
             v = v.detach().cpu().numpy() if isinstance(v, torch.Tensor) else np.asarray(v)
             if v.shape != self.shapes[key]:
@@ -64,7 +102,7 @@ class ParamLayout:
         from collections import OrderedDict
         flat = flat.detach().cpu().numpy() if isinstance(flat, torch.Tensor) else np.asarray(flat)
         sd = OrderedDict()
-        for key, name, tr in STATE_KEYS:
+        for key, name, tr in self.keys:
             shp = self.shapes[key]
             n = int(np.prod(shp))
             o = self.offsets[name]
@@ -76,13 +114,13 @@ class ParamLayout:
         return sd
 
     def unflatten_batch(self, flats):
-        """[E, total] flat vectors -> per state_dict key (STATE_KEYS order) a C-contiguous fp64 [E, *shape] array,
+        """[E, total] flat vectors -> per state_dict key (self.keys order) a C-contiguous fp64 [E, *shape] array,
         row i equal to unflatten(flats[i])[key].  A torch tensor (e.g. on the GPU) is converted and transposed
         where it lives, then copied to the host once per key."""
         if isinstance(flats, torch.Tensor):
             E = flats.shape[0]
             out = []
-            for key, name, tr in STATE_KEYS:
+            for key, name, tr in self.keys:
                 shp = self.shapes[key]
                 n = int(np.prod(shp))
                 o = self.offsets[name]
@@ -94,7 +132,7 @@ class ParamLayout:
         flats = np.asarray(flats)
         E = flats.shape[0]
         out = []
-        for key, name, tr in STATE_KEYS:
+        for key, name, tr in self.keys:
             shp = self.shapes[key]
             n = int(np.prod(shp))
             o = self.offsets[name]
@@ -109,7 +147,7 @@ class ParamLayout:
         if not opt_state:
             return np.zeros(self.total, np.float32), np.zeros(self.total, np.float32), 0
         ms, vs, steps = {}, {}, set()
-        for i, (key, _, _) in enumerate(STATE_KEYS):
+        for i, (key, _, _) in enumerate(self.keys):
             st = opt_state.get(i)
             if st is None:  # parameter never received a gradient: torch keeps no state for it
                 ms[key] = vs[key] = np.zeros(self.shapes[key])
@@ -125,4 +163,4 @@ class ParamLayout:
         if step == 0:
             return {}
         return {i: {'step': torch.tensor(float(step), dtype=dtype), 'exp_avg': ms[key], 'exp_avg_sq': vs[key]}
-                for i, (key, _, _) in enumerate(STATE_KEYS)}
+                for i, (key, _, _) in enumerate(self.keys)}

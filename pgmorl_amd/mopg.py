@@ -53,7 +53,8 @@ class MOPGPopulation:
         if self.tb is not None:
             return self.tb.layout
         spec = make_spec(self.args.env_name)
-        return ParamLayout(spec['obs_dim'], spec['act_dim'], spec['obj_num'])
+        return ParamLayout(spec['obs_dim'], spec['act_dim'], spec['obj_num'],
+                           layernorm=bool(getattr(self.args, 'layernorm', False)))
 
     def _batch(self, P):
         """The one TaskBatch of this runtime, P active task slots.  Allocated once (re-allocated only when a
@@ -69,7 +70,7 @@ class MOPGPopulation:
                                 obj_rms=a.obj_rms, raw=a.raw, clip_param=a.clip_param, ppo_epoch=a.ppo_epoch,
                                 num_mini_batch=a.num_mini_batch, value_loss_coef=a.value_loss_coef,
                                 entropy_coef=a.entropy_coef, max_grad_norm=a.max_grad_norm, device=self.device,
-                                capacity=cap)
+                                capacity=cap, layernorm=bool(getattr(a, 'layernorm', False)))
         else:
             self.tb.set_active(P)
         return self.tb

@@ -39,7 +39,8 @@ def initialize_warm_up_batch(args, runtime):
     layout = runtime._batch(len(weights_batch)).layout
     dev = runtime.device
     for w in weights_batch:
-        pol = new_policy(spec['obs_dim'], spec['act_dim'], args.obj_num)
+        pol = new_policy(spec['obs_dim'], spec['act_dim'], args.obj_num,
+                         layernorm=bool(getattr(args, 'layernorm', False)))
         flat = torch.from_numpy(layout.flatten(pol.state_dict())).to(dev)
         snap = DeviceSnapshot(layout, flat, torch.zeros_like(flat), torch.zeros_like(flat), 0)
         env_params = {'ob_rms': RunningMeanStd(shape=(spec['obs_dim'],)) if args.ob_rms else None,

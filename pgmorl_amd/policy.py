@@ -3,7 +3,8 @@
 Initial parameters come from torch exactly as the reference draws them: under float64 default
 dtype (morl/run.py:53), each ``nn.Linear`` default init followed by an orthogonal re-init
 (gain sqrt(2) for the towers and value head, 1 for the action mean), including MLPBase's
-discarded 1-output critic head, in module-construction order (a2c_ppo_acktr/model.py:201-256,
+discarded 1-output critic head, in module-construction order; ``layernorm=True`` builds the
+Linear(bias=False) -> LayerNorm -> tanh towers, whose LayerNorms draw nothing (a2c_ppo_acktr/model.py:201-256,
 distributions.py:71-79, utils.py:53-57).  This is plumbing at the warm-up boundary; the hot path
 never runs on the CPU.
 
@@ -34,18 +35,26 @@ class _Gaussian(nn.Module):
 
 
 class _Base(nn.Module):
-    def __init__(self, obs_dim, obj_num, hidden):
+    def __init__(self, obs_dim, obj_num, hidden, layernorm=False):
         super().__init__()
         gain = np.sqrt(2)
 
-        def lin(i, o):
-            m = nn.Linear(i, o)
+        def lin(i, o, bias=True):
+            m = nn.Linear(i, o, bias=bias)  # bias=False draws only the weight
             nn.init.orthogonal_(m.weight.data, gain=gain)
-            nn.init.constant_(m.bias.data, 0.0)
+            if bias:
+                nn.init.constant_(m.bias.data, 0.0)
             return m
 
-        self.actor = nn.Sequential(lin(obs_dim, hidden), nn.Tanh(), lin(hidden, hidden), nn.Tanh())
-        self.critic = nn.Sequential(lin(obs_dim, hidden), nn.Tanh(), lin(hidden, hidden), nn.Tanh())
+        def tower():
+            if not layernorm:
+                return nn.Sequential(lin(obs_dim, hidden), nn.Tanh(), lin(hidden, hidden), nn.Tanh())
+            # model.py:211-226: Linear(bias=False) -> LayerNorm (gamma 1, beta 0, no RNG draw) -> Tanh, twice
+            return nn.Sequential(lin(obs_dim, hidden, False), nn.LayerNorm(hidden, elementwise_affine=True), nn.Tanh(),
+                                 lin(hidden, hidden, False), nn.LayerNorm(hidden, elementwise_affine=True), nn.Tanh())
+
+        self.actor = tower()
+        self.critic = tower()
         self.critic_linear = lin(hidden, 1)         # MLPBase head: drawn, then replaced
         self.critic_linear = lin(hidden, obj_num)   # MOMLPBase head
 
@@ -53,16 +62,16 @@ class _Base(nn.Module):
 class Policy(nn.Module):
     """Parameter container with the reference's module tree / state_dict keys."""
 
-    def __init__(self, obs_dim, act_dim, obj_num, hidden=64):
+    def __init__(self, obs_dim, act_dim, obj_num, hidden=64, layernorm=False):
         super().__init__()
-        self.base = _Base(obs_dim, obj_num, hidden)
+        self.base = _Base(obs_dim, obj_num, hidden, layernorm)
         self.dist = _Gaussian(hidden, act_dim)
 
 
-def new_policy(obs_dim, act_dim, obj_num, hidden=64):
+def new_policy(obs_dim, act_dim, obj_num, hidden=64, layernorm=False):
     prev = torch.get_default_dtype()
     torch.set_default_dtype(torch.float64)
     try:
-        return Policy(obs_dim, act_dim, obj_num, hidden).double()
+        return Policy(obs_dim, act_dim, obj_num, hidden, layernorm).double()
     finally:
         torch.set_default_dtype(prev)

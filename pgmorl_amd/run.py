@@ -93,8 +93,15 @@ def main(argv=None):
     argv = sys.argv[1:] if argv is None else argv
     torch.set_default_dtype(torch.float64)
     args = get_parser().parse_args(merge_argv(argv))
-    if args.layernorm:
-        raise NotImplementedError('--layernorm towers are not implemented by the MI355X kernels')
+    if args.layernorm:  # refused here, before the save dir or the device is touched
+        from ._lib import PGMError
+        from .envspec import make_spec
+        from .runtime import LN_MAX_OBS
+        obs_dim = make_spec(args.env_name)['obs_dim']
+        if obs_dim > LN_MAX_OBS:
+            raise PGMError(f'--layernorm with {args.env_name}: the LayerNorm kernels keep layer 1 LDS-resident and '
+                           f'are built for obs_dim <= {LN_MAX_OBS}; obs_dim {obs_dim} would need a streamed layer-1 '
+                           f'LayerNorm kernel, which does not exist')
     os.makedirs(args.save_dir, exist_ok=True)
     with open(os.path.join(args.save_dir, 'args.txt'), 'w') as fp:
         fp.write(str(merge_argv(argv)))

@@ -21,6 +21,7 @@ from ._lib import (Dims, EnvSpec, EnvState, NormState, PGMError, PPOHParams, Rol
 from .layout import ParamLayout
 
 F32, F64, I32 = torch.float32, torch.float64, torch.int32
+LN_MAX_OBS = 32  # layernorm=True: the five envs with obs_dim <= 32 (include/pgm_abi.h pgm_dims.LN)
 UPDATE_TIMEOUT_MSG = ('pgm_ppo_update: a cross-workgroup exchange timed out (workspace word 2P set); the update '
                       'kernel\'s workgroups were not co-resident -- the parameters are invalid')
 
@@ -51,7 +52,8 @@ class TaskBatch:
     def __init__(self, env_name, P, num_processes=4, num_steps=2048, seed=0, eval_num=1, gamma=0.995,
                  gae_lambda=0.95, use_gae=True, use_proper_time_limits=True, ob_rms=True, obj_rms=True, raw=True,
                  clip_param=0.2, ppo_epoch=10, num_mini_batch=32, value_loss_coef=0.5, entropy_coef=0.0,
-                 max_grad_norm=0.5, adam_eps=1e-5, use_clipped_value_loss=True, device='cuda', capacity=None):
+                 max_grad_norm=0.5, adam_eps=1e-5, use_clipped_value_loss=True, device='cuda', capacity=None,
+                 layernorm=False):
         self.spec = envspec.make_spec(env_name)
         sp = self.spec
         self.env_name = env_name
@@ -63,7 +65,12 @@ class TaskBatch:
         self.use_ob_rms, self.use_obj_rms, self.raw = ob_rms, obj_rms, raw
         self.ppo_epoch, self.num_mini_batch = ppo_epoch, num_mini_batch
         self.dev = torch.device(device)
-        self.layout = ParamLayout(self.O, self.A, self.K, self.H)
+        self.layernorm = bool(layernorm)
+        if self.layernorm and self.O > LN_MAX_OBS:
+            raise PGMError(f'layernorm=True with {env_name}: the LayerNorm kernels keep layer 1 LDS-resident and are '
+                           f'built for obs_dim <= {LN_MAX_OBS}; obs_dim {self.O} would need a streamed layer-1 '
+                           f'LayerNorm kernel, which does not exist')
+        self.layout = ParamLayout(self.O, self.A, self.K, self.H, layernorm=self.layernorm)
         L, O, A, K, N, T = self.layout.total, self.O, self.A, self.K, self.N, self.T
         self._full = {}  # name -> full-capacity tensor whose leading dim is the task slot
 
@@ -117,7 +124,7 @@ class TaskBatch:
                              use_clipped_value_loss=int(use_clipped_value_loss))
         self._eval_stream, self._eval_done = None, None
         self._reset_pending = False  # a pgm_ppo_update_reset queued on the side stream, not yet waited for
-        nws = lib().pgm_ppo_update_workspace_bytes(C.byref(Dims(Pc, N, T, O, A, K, self.H)))
+        nws = lib().pgm_ppo_update_workspace_bytes(C.byref(Dims(Pc, N, T, O, A, K, self.H, int(self.layernorm))))
         self.update_ws = torch.zeros((nws + 7) // 8, dtype=torch.int64, device=self.dev)
         # sticky OR of every update's exchange-timeout word (workspace word 2P, include/pgm_abi.h): a launch
         # whose spin-wait gave up produced invalid parameters; check_update() turns that into PGMError
@@ -177,7 +184,7 @@ class TaskBatch:
 
     # ------------------------------------------------------------------ structs
     def _build_structs(self):
-        self.dims = Dims(self.P, self.N, self.T, self.O, self.A, self.K, self.H)
+        self.dims = Dims(self.P, self.N, self.T, self.O, self.A, self.K, self.H, int(self.layernorm))
         st = self._spec_t
         self.c_spec = EnvSpec(_ptr(st['d']), _ptr(st['U']), _ptr(st['c']), _ptr(st['V']), _ptr(st['ebase']),
                               _ptr(st['ecoef']), _ptr(st['act_lo']), _ptr(st['act_hi']),
@@ -224,7 +231,7 @@ class TaskBatch:
     def act(self, obs, noise=None, deterministic=False):
         P, N = self.P, obs.shape[1]
         obs = obs.to(device=self.dev, dtype=F32).contiguous()
-        d = Dims(P, N, self.T, self.O, self.A, self.K, self.H)
+        d = Dims(P, N, self.T, self.O, self.A, self.K, self.H, int(self.layernorm))
         value = torch.empty(P, N, self.K, dtype=F32, device=self.dev)
         action = torch.empty(P, N, self.A, dtype=F32, device=self.dev)
         logp = torch.empty(P, N, dtype=F32, device=self.dev)

@@ -27,6 +27,12 @@
  *                          (+ feed_forward_generator storage.py:118-154, clip_grad_norm_, Adam)
  *                          (pgm_ppo_update_reset: its workspace reset, issued ahead on another stream)
  *   pgm_eval              evaluation()                       morl/mopg.py:25-46
+ *   pgm_rollout_act       Policy.act / get_value of one rollout step, into the strided storage slots
+ *                                                           morl/mopg.py:105-108, 132-135
+ *   pgm_env_ingest        VecNormalize.step_wait / reset + RolloutStorage.insert on a HOST env's transition
+ *                                                           vec_normalize.py:29-66, morl/mopg.py:110-130,
+ *                                                           storage.py:50-62
+ *   pgm_eval_act          evaluation()'s normalise + deterministic act for a HOST env   morl/mopg.py:36-39
  *   pgm_randperm          SubsetRandomSampler's randperm     (perf-mode RNG replacement)
  *   pgm_normal_noise      Normal.sample's torch.normal draw  (perf-mode RNG replacement)
  *
@@ -54,6 +60,9 @@ extern "C" {
 #endif
 
 #define PGM_ABI_VERSION 5
+/* Additions that change no existing struct or entry point raise the minor only.
+ * Minor 1: pgm_abi_minor, pgm_rollout_act, pgm_env_ingest, pgm_eval_act (host-stepped environments). */
+#define PGM_ABI_MINOR 1
 
 #define PGM_OK 0
 #define PGM_E_INVALID_ARG (-1)
@@ -180,6 +189,7 @@ typedef struct pgm_ppo_hparams {
 } pgm_ppo_hparams;
 
 int pgm_abi_version(void);
+int pgm_abi_minor(void); /* PGM_ABI_MINOR; a library without this symbol is minor 0 */
 const char* pgm_last_error(void);
 
 /* Flat per-task parameter layout: offsets[PGM_NUM_PARAM_TENSORS] (floats) and the padded
@@ -274,6 +284,46 @@ int pgm_ppo_fs_fragment_map(int32_t O, int32_t A, int32_t K, int32_t m, int32_t*
 int pgm_eval(const pgm_dims* d, const float* params, const pgm_env_spec* spec, const double* ob_mean,
              const double* ob_var, const double* s0_eval, int32_t eval_num, int32_t use_ob_rms, int32_t raw,
              double gamma, double* objs_out, const pgm_launch_opts* opts, pgm_stream_t stream);
+
+/* ---- Host-stepped environments (from minor 1).  The environments run on the host; policy, VecNormalize
+ * statistics, rollout storage and the PPO update stay on the device.  One rollout step t is
+ *     pgm_rollout_act(t) -> copy action_out to the host -> envs.step(actions) -> copy the transition to the device
+ *     -> pgm_env_ingest(t)
+ * and pgm_rollout_act(T) after the last step writes the bootstrap value.  Neither touches a storage slot other than
+ * the ones named below; pgm_env_spec and the synthetic dynamics play no part.
+ *
+ * Policy.act for rollout step t of every task (morl/mopg.py:105-108; t == T: get_value, :132-135).  Reads
+ * rb->obs[p][t].  0 <= t < T: writes rb->values[p][t], rb->actions[p][t], rb->logp[p][t] and the raw (unclipped)
+ * sampled action into action_out [P][N][A]; noise is the base of the [T][N][A] stream pgm_rollout takes (slice t is
+ * read) and is required.  t == T: writes rb->values[p][T] only; noise and action_out may be NULL.  Other t:
+ * PGM_E_SHAPE.  d->LN as pgm_act_forward. */
+int pgm_rollout_act(const pgm_dims* d, const float* params, const pgm_rollout_buf* rb, int32_t t,
+                    const float* noise, float* action_out, pgm_stream_t stream);
+
+/* VecNormalize.step_wait + RolloutStorage.insert on one externally produced transition per env
+ * (vec_normalize.py:29-66, morl/mopg.py:110-130, storage.py:50-62, the .float() of a2c_ppo_acktr/envs.py:192).
+ * raw_obs fp64 [P][N][O] is what DummyVecEnv.step_wait returned (for a done env already its reset observation),
+ * raw_obj fp64 [P][N][K] the step's info['obj'], reward fp64 [P][N] the scalar env reward (feeds ret / ret_rms),
+ * done / bad_transition int32 [P][N]; all device pointers.
+ * 0 <= t < T: ret = ret*gamma + reward; obj = obj*gamma + raw_obj (raw_obj while obj_acc_valid == 0); ob_rms update,
+ * normalise, clip; ret_rms update; obj_rms update, scale and clip the objectives; zero ret / obj of done envs.
+ * Writes rb->obs[p][t+1] (fp32), rb->rewards[p][t], rb->masks[p][t+1] = !done, rb->bad_masks[p][t+1] =
+ * !bad_transition.
+ * t == -1: a fresh make_vec_envs + reset(): ret = 0, obj_acc_valid = 0, ob_rms update + normalise; writes
+ * rb->obs[p][0], masks[p][0] = bad_masks[p][0] = 1; raw_obj, reward, done, bad_transition may be NULL.
+ * Other t: PGM_E_SHAPE.  Reads and writes st->obj_acc, st->obj_acc_valid, st->ret and all of ns; st->s,
+ * st->elapsed, st->s0 are not read and may be NULL. */
+int pgm_env_ingest(const pgm_dims* d, const pgm_env_state* st, const pgm_norm_state* ns,
+                   const pgm_rollout_buf* rb, int32_t t, const double* raw_obs, const double* raw_obj,
+                   const double* reward, const int32_t* done, const int32_t* bad_transition,
+                   pgm_stream_t stream);
+
+/* The evaluation forward with frozen statistics (morl/mopg.py:36-39): raw_obs fp64 [P][E][O], 1 <= E <= 8, is
+ * normalised in fp64 as clip((ob - mean) / sqrt(var + 1e-8), -10, 10) when use_ob_rms (ob_mean / ob_var [P][O]), cast
+ * to fp32 (never rounded to fp32 first) and action_out [P][E][A] receives the deterministic action dist.mean.
+ * d->N and d->T are ignored.  d->LN as pgm_act_forward. */
+int pgm_eval_act(const pgm_dims* d, const float* params, const double* ob_mean, const double* ob_var,
+                 int32_t use_ob_rms, const double* raw_obs, int32_t E, float* action_out, pgm_stream_t stream);
 
 /* count independent random permutations of [0, n) into out [count][n] (int32), keyed by seed. */
 int pgm_randperm(int32_t n, int32_t count, uint64_t seed, int32_t* out, pgm_stream_t stream);

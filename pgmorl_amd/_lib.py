@@ -15,6 +15,7 @@ LIB_PATH = os.environ.get('PGM_LIB') or os.path.join(HERE, 'libpgm.so')
 TEST_LIB_PATH = os.path.join(HERE, 'libpgm_test.so')  # -DPGM_TEST_HOOKS build (pgmorl_amd/build.py), tests only
 
 PGM_ABI_VERSION = 5
+PGM_ABI_MINOR = 1  # pgm_abi_minor(): the host-stepped environment entry points exist from minor 1
 PGM_OK, PGM_E_INVALID_ARG, PGM_E_SHAPE, PGM_E_HIP, PGM_E_UNSUPPORTED = 0, -1, -2, -3, -4
 PARAM_TENSORS = ['actor_w1', 'actor_b1', 'actor_w2', 'actor_b2', 'critic_w1', 'critic_b1', 'critic_w2',
                  'critic_b2', 'value_w', 'value_b', 'mean_w', 'mean_b', 'logstd']
@@ -111,6 +112,12 @@ _SIGS = {
                            C.POINTER(LaunchOpts), P_]),
     'pgm_randperm': (C.c_int, [I32, I32, C.c_uint64, P_, P_]),
     'pgm_normal_noise': (C.c_int, [C.c_int64, C.c_uint64, P_, P_]),
+    # host-stepped environments (ABI minor 1)
+    'pgm_abi_minor': (C.c_int, []),
+    'pgm_rollout_act': (C.c_int, [C.POINTER(Dims), P_, C.POINTER(RolloutBuf), I32, P_, P_, P_]),
+    'pgm_env_ingest': (C.c_int, [C.POINTER(Dims), C.POINTER(EnvState), C.POINTER(NormState), C.POINTER(RolloutBuf),
+                                 I32, P_, P_, P_, P_, P_, P_]),
+    'pgm_eval_act': (C.c_int, [C.POINTER(Dims), P_, P_, P_, I32, P_, I32, P_, P_]),
 }
 
 EXPORTS = tuple(_SIGS)

@@ -127,6 +127,8 @@ extern "C" {
 
 int pgm_abi_version(void) { return PGM_ABI_VERSION; }
 
+int pgm_abi_minor(void) { return PGM_ABI_MINOR; }
+
 const char* pgm_last_error(void) { return pgm::g_err; }
 
 int pgm_param_layout(int32_t O, int32_t A, int32_t K, int32_t H, int32_t* offsets, int32_t* total) {

@@ -1,0 +1,275 @@
+"""Host-stepped environments: the vectorised env side of ``TaskBatch(host_env=...)``.
+
+The environments run on the CPU; ``Policy.act``, VecNormalize, the rollout storage, GAE and the PPO update stay on the
+device (pgm_rollout_act / pgm_env_ingest / pgm_eval_act, include/pgm_abi.h).  A ``HostVecEnv`` is P tasks x N
+environments behind one ``step``: what the reference's per-task ``DummyVecEnv`` of N ``make_env`` thunks returns
+(a2c_ppo_acktr/envs.py:84-119, dummy_vec_env.py:45-62), stacked over the tasks, with no normalisation applied -- raw
+fp64 observations, the scalar env reward, ``info['obj']`` and the done / bad_transition flags.
+
+* ``SynthHostVecEnv``  SynthMO (envspec.py) in numpy fp64: the stand-in that exercises the whole path without MuJoCo.
+* ``GymHostVecEnv``    any ``make_env(env_name, seed, rank)`` returning gym-style objects (duck-typed: gym itself is
+                       never imported here), in the 4-tuple or the 5-tuple step API.
+"""
+import importlib
+from concurrent.futures import ThreadPoolExecutor
+
+import numpy as np
+
+from . import envspec
+
+MAX_WORKERS = 16  # cap of GymHostVecEnv's optional thread pool (never sized from the machine's CPU count)
+
+
+class HostVecEnv:
+    """The protocol ``TaskBatch`` drives.  Attributes: ``P`` (active tasks), ``N`` (envs per task), ``obs_dim``,
+    ``act_dim``, ``obj_num``.  Every task's env n is seeded ``seed + n`` (each task process of the reference builds
+    its own ``make_vec_envs(env_name, seed, N)``, morl/mopg.py:67-69)."""
+    P = N = obs_dim = act_dim = obj_num = 0
+
+    def set_active(self, P):
+        """Use the first P tasks (P <= the P of construction); followed by ``reset()``."""
+        raise NotImplementedError
+
+    def reset(self):
+        """Fresh episodes everywhere -> obs f64 [P, N, O]."""
+        raise NotImplementedError
+
+    def step(self, actions):
+        """actions f32 [P, N, A] (raw policy samples; the env clips) -> (obs f64 [P, N, O], reward f64 [P, N],
+        done bool [P, N], bad bool [P, N], obj f64 [P, N, K]).  DummyVecEnv semantics: a done env is reset and obs is
+        its reset observation, obj / reward / flags are the terminal step's.  bad: the episode ended at a time
+        limit (TimeLimitMask's bad_transition), not in a true terminal state."""
+        raise NotImplementedError
+
+    def eval_reset(self, eval_num):
+        """eval_num fresh evaluation episodes per task, episode e seeded ``seed + e`` (morl/mopg.py:30-33)
+        -> obs f64 [P, E, O]."""
+        raise NotImplementedError
+
+    def eval_step(self, actions):
+        """actions f32 [P, E, A] -> (obs f64 [P, E, O], obj f64 [P, E, K], done bool [P, E]).  No auto-reset: an
+        ended episode's later outputs are masked by the caller."""
+        raise NotImplementedError
+
+    def close(self):
+        pass
+
+    def dims(self):
+        return self.obs_dim, self.act_dim, self.obj_num
+
+
+class SynthHostVecEnv(HostVecEnv):
+    """SynthMO on the host, fp64: a_c = clip(a, lo, hi); s' = tanh(d s + U a_c + c); obj = V s' + ebase - ecoef
+    sum(a_c^2); scalar reward 0; done at ``max_episode_steps`` (bad_transition set), then auto-reset to the env's
+    reset state.  Constants and reset states are envspec's, so it is the device envs' dynamics exactly."""
+
+    def __init__(self, env_name, P, N, seed=0, max_episode_steps=None):
+        sp = envspec.make_spec(env_name)
+        self.spec = sp
+        self.env_name, self.seed = env_name, seed
+        self.capacity = self.P = P
+        self.N = N
+        self.obs_dim, self.act_dim, self.obj_num = sp['obs_dim'], sp['act_dim'], sp['obj_num']
+        self.max_episode_steps = int(max_episode_steps or sp['max_episode_steps'])
+        self.s0 = envspec.reset_table(self.obs_dim, seed, N)  # [N, O]: env n of every task
+        self.s = self.elapsed = None
+        self._es = self._eel = None
+
+    def set_active(self, P):
+        if not 0 < P <= self.capacity:
+            raise ValueError(f'active tasks {P} outside [1, {self.capacity}]')
+        self.P = P
+        self.s = self.elapsed = None
+
+    def _dynamics(self, s, actions):
+        sp = self.spec
+        a_c = np.clip(np.asarray(actions, dtype=np.float64), sp['act_lo'], sp['act_hi'])
+        s = np.tanh(sp['d'] * s + np.einsum('oa,pna->pno', sp['U'], a_c) + sp['c'])
+        obj = (np.einsum('ko,pno->pnk', sp['V'], s) + sp['ebase']
+               - sp['ecoef'] * np.sum(np.square(a_c), axis=-1, keepdims=True))
+        return s, obj
+
+    def terminal(self, s, obj):
+        """True terminal states [P, N] of the step just taken (none in SynthMO; a subclass may end episodes early)."""
+        return np.zeros(s.shape[:2], dtype=bool)
+
+    def reset(self):
+        self.s = np.broadcast_to(self.s0, (self.P, self.N, self.obs_dim)).copy()
+        self.elapsed = np.zeros((self.P, self.N), dtype=np.int64)
+        return self.s.copy()
+
+    def step(self, actions):
+        self.s, obj = self._dynamics(self.s, actions)
+        self.elapsed += 1
+        limit = self.elapsed >= self.max_episode_steps
+        term = self.terminal(self.s, obj)
+        done = limit | term
+        bad = limit & ~term
+        if done.any():
+            self.s[done] = np.broadcast_to(self.s0, self.s.shape)[done]
+            self.elapsed[done] = 0
+        return self.s.copy(), np.zeros((self.P, self.N)), done, bad, obj
+
+    def eval_reset(self, eval_num):
+        s0 = envspec.reset_table(self.obs_dim, self.seed, eval_num)
+        self._es = np.broadcast_to(s0, (self.P, eval_num, self.obs_dim)).copy()
+        self._eel = np.zeros((self.P, eval_num), dtype=np.int64)
+        return self._es.copy()
+
+    def eval_step(self, actions):
+        self._es, obj = self._dynamics(self._es, actions)
+        self._eel += 1
+        done = (self._eel >= self.max_episode_steps) | self.terminal(self._es, obj)
+        return self._es.copy(), obj, done
+
+
+def _reset_obs(r):
+    """env.reset(): obs (old API) or (obs, info) (new API)."""
+    if isinstance(r, tuple) and len(r) == 2 and isinstance(r[1], dict):
+        r = r[0]
+    return np.asarray(r, dtype=np.float64).reshape(-1)
+
+
+def _step_env(env, action):
+    """One env.step in either API -> (obs, reward, done, bad, obj)."""
+    r = env.step(action)
+    if len(r) == 5:  # obs, reward, terminated, truncated, info
+        obs, rew, term, trunc, info = r
+        done, bad = bool(term) or bool(trunc), bool(trunc) and not bool(term)
+    else:  # obs, reward, done, info: TimeLimitMask's key, or gym's own TimeLimit flag
+        obs, rew, done, info = r
+        done = bool(done)
+        bad = 'bad_transition' in info or bool(info.get('TimeLimit.truncated', False))
+    return (np.asarray(obs, dtype=np.float64).reshape(-1), float(rew), done, bad,
+            np.asarray(info['obj'], dtype=np.float64).reshape(-1))
+
+
+def probe_dims(env):
+    """(obs_dim, act_dim, obj_num) of one gym-style multi-objective env (resets it; may step it once)."""
+    obs = _reset_obs(env.reset())
+    act_dim = int(np.prod(env.action_space.shape))
+    inner = getattr(env, 'unwrapped', env)
+    obj_num = getattr(inner, 'obj_dim', None)
+    if obj_num is None:
+        obj_num = _step_env(env, np.zeros(act_dim, dtype=np.float32))[4].size
+        env.reset()
+    return obs.size, act_dim, int(obj_num)
+
+
+class GymHostVecEnv(HostVecEnv):
+    """P x N env objects from ``make_env(env_name, seed, rank)`` (rank n of every task: the env is expected to be
+    seeded ``seed + rank``, as a2c_ppo_acktr/envs.py:47 does), stepped in a host loop or by ``workers`` threads.
+    Evaluation episodes run on fresh ``make_env(env_name, seed, eval_id)`` objects, i.e. seeded ``seed + eval_id``."""
+
+    def __init__(self, make_env, env_name, P, N, seed=0, workers=0):
+        self.make_env, self.env_name, self.seed = make_env, env_name, seed
+        self.capacity = self.P = P
+        self.N = N
+        self.envs = [[make_env(env_name, seed, n) for n in range(N)] for _ in range(P)]
+        self.obs_dim, self.act_dim, self.obj_num = probe_dims(self.envs[0][0])
+        self._eval = []
+        workers = min(MAX_WORKERS, int(workers), P * N)
+        self._pool = ThreadPoolExecutor(max_workers=workers) if workers > 1 else None
+
+    def _map(self, fn, items):
+        return list(self._pool.map(fn, items)) if self._pool is not None else [fn(x) for x in items]
+
+    def set_active(self, P):
+        if not 0 < P <= self.capacity:
+            raise ValueError(f'active tasks {P} outside [1, {self.capacity}]')
+        self.P = P
+
+    def reset(self):
+        flat = [e for row in self.envs[:self.P] for e in row]
+        obs = self._map(lambda e: _reset_obs(e.reset()), flat)
+        return np.stack(obs).reshape(self.P, self.N, self.obs_dim)
+
+    def step(self, actions):
+        actions = np.asarray(actions)
+        jobs = [(self.envs[p][n], actions[p, n]) for p in range(self.P) for n in range(self.N)]
+
+        def one(job):
+            env, a = job
+            obs, rew, done, bad, obj = _step_env(env, a)
+            if done:  # DummyVecEnv auto-reset: the returned observation is the next episode's first
+                obs = _reset_obs(env.reset())
+            return obs, rew, done, bad, obj
+        out = self._map(one, jobs)
+        P, N = self.P, self.N
+        return (np.stack([o[0] for o in out]).reshape(P, N, self.obs_dim),
+                np.array([o[1] for o in out], dtype=np.float64).reshape(P, N),
+                np.array([o[2] for o in out], dtype=bool).reshape(P, N),
+                np.array([o[3] for o in out], dtype=bool).reshape(P, N),
+                np.stack([o[4] for o in out]).reshape(P, N, self.obj_num))
+
+    def _close_eval(self):
+        for row in self._eval:
+            for e in row:
+                if hasattr(e, 'close'):
+                    e.close()
+        self._eval = []
+
+    def eval_reset(self, eval_num):
+        self._close_eval()
+        self._eval = [[self.make_env(self.env_name, self.seed, e) for e in range(eval_num)] for _ in range(self.P)]
+        self._eval_done = np.zeros((self.P, eval_num), dtype=bool)
+        obs = [_reset_obs(e.reset()) for row in self._eval for e in row]
+        self._eval_obs = np.stack(obs).reshape(self.P, eval_num, self.obs_dim)
+        return self._eval_obs.copy()
+
+    def eval_step(self, actions):
+        actions = np.asarray(actions)
+        E = self._eval_done.shape[1]
+        obj = np.zeros((self.P, E, self.obj_num))
+        for p in range(self.P):
+            for e in range(E):
+                if self._eval_done[p, e]:  # an ended episode is not stepped again
+                    continue
+                o, _, done, _, ob = _step_env(self._eval[p][e], actions[p, e])
+                self._eval_obs[p, e], obj[p, e], self._eval_done[p, e] = o, ob, done
+        return self._eval_obs.copy(), obj, self._eval_done.copy()
+
+    def close(self):
+        self._close_eval()
+        if self._pool is not None:
+            self._pool.shutdown()
+            self._pool = None
+        for row in self.envs:
+            for e in row:
+                if hasattr(e, 'close'):
+                    e.close()
+
+
+def resolve(spec):
+    """``--host-env SPEC`` -> factory(env_name, P, N, seed) of a HostVecEnv.  ``synth``: SynthHostVecEnv;
+    ``module:callable``: GymHostVecEnv over ``callable(env_name, seed, rank)``.  Raises ValueError for a spec that
+    cannot be imported."""
+    if spec == 'synth':
+        return SynthHostVecEnv
+    mod, sep, name = str(spec).partition(':')
+    if not sep or not mod or not name:
+        raise ValueError(f'--host-env {spec!r}: expected "synth" or "module:callable"')
+    try:
+        fn = getattr(importlib.import_module(mod), name)
+    except (ImportError, AttributeError) as e:
+        raise ValueError(f'--host-env {spec!r}: cannot import ({e})') from e
+    if not callable(fn):
+        raise ValueError(f'--host-env {spec!r}: {name} is not callable')
+    return lambda env_name, P, N, seed=0: GymHostVecEnv(fn, env_name, P, N, seed)
+
+
+def check_spec(spec, env_name, seed=0):
+    """Refuse, before anything is written or allocated, a --host-env whose env dims are not envspec's for env_name
+    (the kernels are compiled for those dims).  Returns the factory."""
+    factory = resolve(spec)
+    want = envspec.make_spec(env_name)
+    want = (want['obs_dim'], want['act_dim'], want['obj_num'])
+    probe = factory(env_name, 1, 1, seed)
+    try:
+        got = probe.dims()
+    finally:
+        probe.close()
+    if tuple(got) != want:
+        raise ValueError(f'--host-env {spec!r}: {env_name} has (obs, act, obj) dims {tuple(got)}, the kernels of '
+                         f'{env_name} are built for {want}')
+    return factory

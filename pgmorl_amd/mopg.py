@@ -38,11 +38,20 @@ def linear_lr(j, total_num_updates, lr, ratio=1.0):
 
 
 class MOPGPopulation:
-    def __init__(self, args, device='cuda', rng='device'):
+    def __init__(self, args, device='cuda', rng='device', host_env=None):
+        """host_env (default ``args.host_env``, the --host-env flag; None = the device envs): 'synth',
+        'module:callable' or a factory (env_name, P, N, seed) -> hostenv.HostVecEnv.  The environments then run on
+        the host and every TaskBatch of this runtime is built over a HostVecEnv of its own task slots (a rank holds
+        host envs for its block of the population only)."""
         self.args = args
         self.device = torch.device(device)
         self.rng = rng
         self.tb = None
+        host_env = getattr(args, 'host_env', None) if host_env is None else host_env
+        if isinstance(host_env, str):
+            from .hostenv import resolve
+            host_env = resolve(host_env)
+        self.host_env_factory = host_env
         self.moved_bytes = 0  # snapshot bytes this rank contributed to move_rows (multi-GPU)
 
     @property
@@ -64,13 +73,18 @@ class MOPGPopulation:
             cap = max(P, getattr(a, 'num_tasks', 0) or 0) if self.tb is None else P
             rank, ws = world()
             cap = min(cap, max(P, -(-cap // ws)))  # a rank only ever holds its block of the population
+            he = None
+            if self.host_env_factory is not None:
+                if self.tb is not None and self.tb.host_env is not None:
+                    self.tb.host_env.close()
+                he = self.host_env_factory(a.env_name, cap, a.num_processes, a.seed)
             self.tb = TaskBatch(a.env_name, P, num_processes=a.num_processes, num_steps=a.num_steps, seed=a.seed,
                                 eval_num=a.eval_num, gamma=a.gamma, gae_lambda=a.gae_lambda, use_gae=a.use_gae,
                                 use_proper_time_limits=a.use_proper_time_limits, ob_rms=a.ob_rms,
                                 obj_rms=a.obj_rms, raw=a.raw, clip_param=a.clip_param, ppo_epoch=a.ppo_epoch,
                                 num_mini_batch=a.num_mini_batch, value_loss_coef=a.value_loss_coef,
                                 entropy_coef=a.entropy_coef, max_grad_norm=a.max_grad_norm, device=self.device,
-                                capacity=cap, layernorm=bool(getattr(a, 'layernorm', False)))
+                                capacity=cap, layernorm=bool(getattr(a, 'layernorm', False)), host_env=he)
         else:
             self.tb.set_active(P)
         return self.tb

@@ -3,7 +3,7 @@
     python -m pgmorl_amd.run --env-name MO-Walker2d-v2 --num-env-steps 5000000 ... [--selection-method ra]
 
 Adds ``--rng {device,host}`` (device counter streams, or the reference's own torch draws for
-bit-compatible runs) and ``--device``.
+bit-compatible runs), ``--device`` and ``--host-env SPEC`` (environments stepped on the host, hostenv.py).
 """
 import argparse
 import os
@@ -60,6 +60,10 @@ def get_parser():
     add('--layernorm', action='store_true', default=False)
     add('--rng', choices=['device', 'host'], default='device')
     add('--device', default='cuda')
+    add('--host-env', default=None, metavar='SPEC',
+        help='step the environments on the host (policy, VecNormalize, storage and PPO stay on the device): '
+             '"synth" (SynthMO in numpy) or "module:callable" with callable(env_name, seed, rank) -> a gym-style '
+             'multi-objective env; default: the device envs')
     return ap
 
 
@@ -102,6 +106,13 @@ def main(argv=None):
             raise PGMError(f'--layernorm with {args.env_name}: the LayerNorm kernels keep layer 1 LDS-resident and '
                            f'are built for obs_dim <= {LN_MAX_OBS}; obs_dim {obs_dim} would need a streamed layer-1 '
                            f'LayerNorm kernel, which does not exist')
+    if args.host_env is not None:  # refused here too: a spec that cannot be imported or whose env dims differ
+        from ._lib import PGMError
+        from .hostenv import check_spec
+        try:
+            check_spec(args.host_env, args.env_name, args.seed)
+        except ValueError as e:
+            raise PGMError(str(e)) from e
     os.makedirs(args.save_dir, exist_ok=True)
     with open(os.path.join(args.save_dir, 'args.txt'), 'w') as fp:
         fp.write(str(merge_argv(argv)))

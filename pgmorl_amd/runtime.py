@@ -9,6 +9,10 @@ statistics, rollout storage) and drives the libpgm kernels on torch's current st
 i.e. one iteration of MOPG_worker's loop body (morl/mopg.py:95-155) for all tasks at once.
 torch is used only for device memory and the stream; every op is a libpgm kernel and raises if
 the library is unavailable (no CPU fallback).
+
+With ``host_env`` (a ``hostenv.HostVecEnv``) the environments run on the host instead: the rollout becomes a per-step
+loop of pgm_rollout_act -> host ``step`` -> pgm_env_ingest and the evaluation a host episode loop over pgm_eval_act;
+returns, advantages and the PPO update are the same kernels on the same storage.
 """
 import ctypes as C
 import math
@@ -53,9 +57,11 @@ class TaskBatch:
                  gae_lambda=0.95, use_gae=True, use_proper_time_limits=True, ob_rms=True, obj_rms=True, raw=True,
                  clip_param=0.2, ppo_epoch=10, num_mini_batch=32, value_loss_coef=0.5, entropy_coef=0.0,
                  max_grad_norm=0.5, adam_eps=1e-5, use_clipped_value_loss=True, device='cuda', capacity=None,
-                 layernorm=False):
+                 layernorm=False, host_env=None):
         self.spec = envspec.make_spec(env_name)
         sp = self.spec
+        self.host_env = host_env
+        self.host_profile = None  # a dict {'act', 'step', 'ingest'} of seconds when a caller wants the split timed
         self.env_name = env_name
         self.capacity = Pc = max(P, capacity or P)
         self.P, self.N, self.T = P, num_processes, num_steps
@@ -130,8 +136,137 @@ class TaskBatch:
         # whose spin-wait gave up produced invalid parameters; check_update() turns that into PGMError
         self.update_failed = torch.zeros(1, dtype=torch.int64, device=self.dev)
         self.last_fail_word = 0
+        if host_env is not None:
+            self._host_alloc(Pc)
         self.set_active(P)
         self.reset_stats()
+
+    # ------------------------------------------------------------------ host-stepped environments
+    HOST_EVAL_MAX = 8  # pgm_eval_act: evaluation episodes per task in one launch
+
+    def _host_alloc(self, Pc):
+        """Pinned host / device staging of the host-env mode: the sampled actions (D2H) and one packed fp64 transition
+        record per step -- raw obs | raw objectives | reward | done, bad_transition as int32 pairs -- so that a
+        step's H2D traffic is one copy."""
+        he, N, O, A, K = self.host_env, self.N, self.O, self.A, self.K
+        if tuple(he.dims()) != (O, A, K) or he.N != N:
+            raise PGMError(f'host_env has (obs, act, obj) dims {tuple(he.dims())} and {he.N} envs per task; '
+                           f'{self.env_name} with num_processes={N} needs {(O, A, K)} and {N}')
+        if getattr(he, 'capacity', he.P) < Pc:
+            raise PGMError(f'host_env holds {getattr(he, "capacity", he.P)} tasks, the batch needs {Pc}')
+        if self.eval_num > self.HOST_EVAL_MAX:
+            raise PGMError(f'host-env mode evaluates at most {self.HOST_EVAL_MAX} episodes per task '
+                           f'(eval_num={self.eval_num})')
+        E = self.eval_num
+        self._h_act = torch.empty(Pc, N, A, dtype=F32, pin_memory=True)
+        self._d_act = torch.zeros(Pc, N, A, dtype=F32, device=self.dev)
+        n = Pc * N * (O + K + 2)
+        self._h_tr = torch.zeros(n, dtype=F64, pin_memory=True)
+        self._d_tr = torch.zeros(n, dtype=F64, device=self.dev)
+        self._tr_ready = None  # the last H2D copy out of _h_tr (the host waits for it before rewriting the buffer)
+        self._h_eobs = torch.zeros(Pc * E * O, dtype=F64, pin_memory=True)
+        self._d_eobs = torch.zeros(Pc * E * O, dtype=F64, device=self.dev)
+        self._h_eact = torch.empty(Pc * E * A, dtype=F32, pin_memory=True)
+        self._d_eact = torch.zeros(Pc * E * A, dtype=F32, device=self.dev)
+
+    def _host_views(self):
+        P, N, O, K = self.P, self.N, self.O, self.K
+        n1, n2, n3 = P * N * O, P * N * K, P * N
+
+        def seg(buf):
+            flags = buf[n1 + n2 + n3:n1 + n2 + 2 * n3].view(I32).view(2, P, N)
+            return (buf[:n1].view(P, N, O), buf[n1:n1 + n2].view(P, N, K), buf[n1 + n2:n1 + n2 + n3].view(P, N),
+                    flags[0], flags[1])
+        self._tr_len = n1 + n2 + 2 * n3
+        self._d_seg = seg(self._d_tr)
+        self._h_seg = tuple(v.numpy() for v in seg(self._h_tr))
+        self.host_env.set_active(P)
+
+    def _ingest(self, t, obs, rew=None, done=None, bad=None, obj=None):
+        """One packed H2D copy of the host transition, then pgm_env_ingest(t) (t = -1: the reset observation)."""
+        if self._tr_ready is not None:
+            self._tr_ready.synchronize()
+        ho, hj, hr, hd, hb = self._h_seg
+        ho[...] = obs
+        if t >= 0:
+            hj[...], hr[...], hd[...], hb[...] = obj, rew, done, bad
+        n = self._tr_len
+        self._d_tr[:n].copy_(self._h_tr[:n], non_blocking=True)
+        self._tr_ready = torch.cuda.Event()
+        self._tr_ready.record()
+        do, dj, dr, dd, db = self._d_seg
+        check(lib().pgm_env_ingest(C.byref(self.dims), C.byref(self.c_state), C.byref(self.c_norm),
+                                   C.byref(self.c_rb), t, _ptr(do), _ptr(dj), _ptr(dr), _ptr(dd), _ptr(db),
+                                   _stream()), 'pgm_env_ingest')
+
+    def _rollout_act(self, t):
+        check(lib().pgm_rollout_act(C.byref(self.dims), _ptr(self.params), C.byref(self.c_rb), t, _ptr(self.noise),
+                                    _ptr(self._d_act), _stream()), 'pgm_rollout_act')
+
+    def _host_rollout(self, seed, noise, carry):
+        """morl/mopg.py:103-135 with the env on the host: per step t the device acts on obs[t], the actions go to the
+        host (pinned D2H + the step's one stream synchronise), the host envs step, the transition returns (pinned
+        H2D) and the device applies VecNormalize + insert into slot t + 1; then the bootstrap value."""
+        import time
+        P, T = self.P, self.T
+        if noise is None:  # the perf-mode counter stream of `seed`: what the fused rollout draws in-kernel
+            check(lib().pgm_normal_noise(self.noise.numel(), C.c_uint64(seed), _ptr(self.noise), _stream()),
+                  'pgm_normal_noise')
+        elif noise is not self.noise:
+            self.noise.copy_(noise.to(dtype=F32))
+        if carry:  # after_update(): slot T -> slot 0 (storage.py:71-75)
+            self.obs[:, 0].copy_(self.obs[:, T])
+            self.masks[:, 0].copy_(self.masks[:, T])
+            self.bad_masks[:, 0].copy_(self.bad_masks[:, T])
+        stream = torch.cuda.current_stream()
+        prof = self.host_profile
+        h_act = self._h_act[:P]
+        a_np = h_act.numpy()
+        for t in range(T):
+            t0 = time.perf_counter()
+            self._rollout_act(t)
+            h_act.copy_(self._d_act[:P], non_blocking=True)
+            stream.synchronize()
+            t1 = time.perf_counter()
+            obs, rew, done, bad, obj = self.host_env.step(a_np)
+            t2 = time.perf_counter()
+            self._ingest(t, obs, rew, done, bad, obj)
+            if prof is not None:
+                stream.synchronize()  # (only when timed: the ingest otherwise overlaps nothing the host waits for)
+                prof['act'] += t1 - t0
+                prof['step'] += t2 - t1
+                prof['ingest'] += time.perf_counter() - t2
+        self._rollout_act(T)
+
+    def _host_evaluate(self, mean, var, out):
+        """evaluation() (morl/mopg.py:25-46) with the episodes on the host: eval_num episodes per task step together,
+        pgm_eval_act normalises with the frozen statistics and returns the deterministic actions; an ended episode
+        stops contributing."""
+        P, E, O, A, K = self.P, self.eval_num, self.O, self.A, self.K
+        he = self.host_env
+        stream = torch.cuda.current_stream()
+        h_obs = self._h_eobs[:P * E * O]
+        h_act = self._h_eact[:P * E * A]
+        obs_np, act_np = h_obs.numpy().reshape(P, E, O), h_act.numpy().reshape(P, E, A)
+        acc = np.zeros((P, E, K))
+        disc = 1.0
+        alive = np.ones((P, E), dtype=bool)
+        obs = he.eval_reset(E)
+        d = Dims(P, 1, 0, O, A, K, self.H, int(self.layernorm))
+        while alive.any():
+            obs_np[...] = obs
+            self._d_eobs[:P * E * O].copy_(h_obs, non_blocking=True)
+            check(lib().pgm_eval_act(C.byref(d), _ptr(self.params), _ptr(mean), _ptr(var), int(self.use_ob_rms),
+                                     _ptr(self._d_eobs), E, _ptr(self._d_eact), _stream()), 'pgm_eval_act')
+            h_act.copy_(self._d_eact[:P * E * A], non_blocking=True)
+            stream.synchronize()
+            obs, obj, done = he.eval_step(act_np)
+            acc += np.where(alive[..., None], disc * np.asarray(obj, dtype=np.float64), 0.0)
+            if not self.raw:
+                disc *= self.gamma
+            alive &= ~np.asarray(done, dtype=bool)
+        out.copy_(torch.from_numpy(acc.sum(1) / E))
+        return out
 
     def set_active(self, P):
         """Run the first P task slots (P <= capacity): re-slices the public views and the kernels' dims."""
@@ -148,6 +283,8 @@ class TaskBatch:
                 self._ob_src = self._stats64[off:off + 2 * self.capacity * w].view(2, self.capacity, w)
         self._eval_mean, self._eval_var = self._eval_ob[0, :P], self._eval_ob[1, :P]
         self._build_structs()
+        if self.host_env is not None:
+            self._host_views()
 
     @property
     def state(self):
@@ -209,6 +346,9 @@ class TaskBatch:
     # ------------------------------------------------------------------ kernels
     def env_reset(self):
         """Fresh make_vec_envs + envs.reset() (mopg.py:67-82): obs[:, 0], masks[:, 0] = 1."""
+        if self.host_env is not None:  # one H2D copy of the host envs' reset observations, then the ingest kernel
+            self._ingest(-1, self.host_env.reset())
+            return self.obs[:, 0]
         out = torch.empty(self.P, self.N, self.O, dtype=F32, device=self.dev)
         check(lib().pgm_env_reset(C.byref(self.dims), C.byref(self.c_spec), C.byref(self.c_state),
                                   C.byref(self.c_norm), _ptr(out), _stream()), 'pgm_env_reset')
@@ -218,6 +358,9 @@ class TaskBatch:
         return out
 
     def env_step(self, action):
+        if self.host_env is not None:
+            raise PGMError('env_step: this batch is in host-env mode (TaskBatch(host_env=...)): the environments are '
+                           'stepped on the host inside rollout(), there is no device env to step')
         P, N, O, K = self.P, self.N, self.O, self.K
         action = action.to(device=self.dev, dtype=F32).contiguous()
         obs = torch.empty(P, N, O, dtype=F32, device=self.dev)
@@ -241,6 +384,8 @@ class TaskBatch:
         return value, action, logp
 
     def rollout(self, seed, noise=None, carry=True):
+        if self.host_env is not None:
+            return self._host_rollout(seed, noise, carry)
         nz = None
         if noise is not None:
             if noise is not self.noise:
@@ -315,6 +460,8 @@ class TaskBatch:
         mean = self.ob_mean if ob_mean is None else ob_mean
         var = self.ob_var if ob_var is None else ob_var
         out = self.objs if out is None else out
+        if self.host_env is not None:
+            return self._host_evaluate(mean, var, out)
         check(lib().pgm_eval(C.byref(self.dims), _ptr(self.params), C.byref(self.c_spec), _ptr(mean), _ptr(var),
                              _ptr(self.s0_eval), self.eval_num, int(self.use_ob_rms), int(self.raw), self.gamma,
                              _ptr(out), C.byref(launch_opts()), _stream()), 'pgm_eval')
@@ -343,7 +490,13 @@ class TaskBatch:
         concurrently with the NEXT iteration's rollout / returns / advantages (which only read the
         parameters); the next PPO update (which writes them) waits for it.  It normalises with a copy of
         this iteration's ob_rms (the next rollout advances the live one) and writes objs_out (default
-        self.objs), readable after wait_eval() or from work queued on eval_stream."""
+        self.objs), readable after wait_eval() or from work queued on eval_stream.
+
+        Host-env mode: the evaluation is a host episode loop that synchronises every step, so there is nothing to
+        overlap: overlap_eval is ignored and the evaluation simply runs after the update, with the live ob_rms
+        (which the next rollout has not advanced yet)."""
+        if self.host_env is not None:
+            overlap_eval = False
         if noise is None:  # perf mode: the counter stream of iteration j, drawn by one wide kernel up front
             check(lib().pgm_normal_noise(self.noise.numel(), C.c_uint64(j), _ptr(self.noise), _stream()),
                   'pgm_normal_noise')

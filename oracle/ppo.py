@@ -108,12 +108,16 @@ def randperms(ppo_epoch, batch_size):
 
 class PPO:
     def __init__(self, actor_critic, clip_param=0.2, ppo_epoch=10, num_mini_batch=32, value_loss_coef=0.5,
-                 entropy_coef=0.0, lr=3e-4, eps=1e-5, max_grad_norm=0.5, use_clipped_value_loss=True):
+                 entropy_coef=0.0, lr=3e-4, eps=1e-5, max_grad_norm=0.5, use_clipped_value_loss=True,
+                 betas=(0.9, 0.999), trace=None):
         self.actor_critic = actor_critic
         self.clip_param, self.ppo_epoch, self.num_mini_batch = clip_param, ppo_epoch, num_mini_batch
         self.value_loss_coef, self.entropy_coef = value_loss_coef, entropy_coef
         self.max_grad_norm, self.use_clipped_value_loss = max_grad_norm, use_clipped_value_loss
-        self.optimizer = optim.Adam(actor_critic.parameters(), lr=lr, eps=eps)
+        self.optimizer = optim.Adam(actor_critic.parameters(), lr=lr, eps=eps, betas=betas)
+        # tests only: a list that receives one record per Adam step (the quantities every branch of the two clipped
+        # losses and of clip_grad_norm_ is decided by); None records nothing.  Recording changes no arithmetic.
+        self.trace = trace
 
     def set_lr(self, lr):
         for g in self.optimizer.param_groups:
@@ -136,8 +140,12 @@ class PPO:
             value_loss = 0.5 * (ret - values).pow(2).mean()
         self.optimizer.zero_grad()
         (value_loss * self.value_loss_coef + action_loss - entropy * self.entropy_coef).backward()
-        nn.utils.clip_grad_norm_(self.actor_critic.parameters(), self.max_grad_norm)
+        total_norm = nn.utils.clip_grad_norm_(self.actor_critic.parameters(), self.max_grad_norm)
         self.optimizer.step()
+        if self.trace is not None:
+            self.trace.append({'ratio': ratio.detach()[:, 0].clone(), 'adv': adv[:, 0].clone(),
+                               'values': values.detach().clone(), 'old_values': vp.clone(), 'returns': ret.clone(),
+                               'grad_norm': float(total_norm)})
         return value_loss.item(), action_loss.item(), entropy.item()
 
     def update(self, rollouts, weights, obj_var, perms=None):

@@ -33,6 +33,15 @@
  *                                                           vec_normalize.py:29-66, morl/mopg.py:110-130,
  *                                                           storage.py:50-62
  *   pgm_eval_act          evaluation()'s normalise + deterministic act for a HOST env   morl/mopg.py:36-39
+ *   pgm_act_forward_cat   Policy.act / get_value with a Categorical head   a2c_ppo_acktr/model.py:33-35,57-73
+ *                          (+ Categorical / FixedCategorical sample, log_probs, mode
+ *                                                           a2c_ppo_acktr/distributions.py:17-27,54-68)
+ *   pgm_rollout_act_cat   the same for one rollout step, into the strided storage slots (one width-1 action per step,
+ *                          a2c_ppo_acktr/storage.py:19-25)   morl/mopg.py:105-108, 132-135
+ *   pgm_eval_act_cat      evaluation()'s normalise + dist.mode() for a HOST env   morl/mopg.py:36-39
+ *   pgm_ppo_update_cat    PPO.update epochs x minibatches with FixedCategorical log_probs / entropy
+ *                                                           a2c_ppo_acktr/algo/ppo.py:58-115, model.py:75-82
+ *   pgm_uniform_noise     Categorical.sample's multinomial draw  (perf-mode RNG replacement)
  *   pgm_randperm          SubsetRandomSampler's randperm     (perf-mode RNG replacement)
  *   pgm_normal_noise      Normal.sample's torch.normal draw  (perf-mode RNG replacement)
  *
@@ -107,6 +116,15 @@ extern "C" {
 #define PGM_PL_MEAN_B 15
 #define PGM_PL_LOGSTD 16     /* dist.logstd._bias       [A] */
 #define PGM_NUM_PARAM_TENSORS_LN 17
+
+/* Discrete action spaces (Categorical head, distributions.py:54-68): the ten tower / value tensors in PGM_P_* order
+ * (indices 0..9), then the head's Linear.  No logstd.  Offsets from pgm_param_layout_cat. */
+#define PGM_PC_LINEAR_W 10   /* dist.linear.weight^T    [H][A]  (A = number of actions) */
+#define PGM_PC_LINEAR_B 11   /* dist.linear.bias        [A] */
+#define PGM_NUM_PARAM_TENSORS_CAT 12
+
+/* pgm_abi_features() bits: additions that leave PGM_ABI_VERSION / PGM_ABI_MINOR alone are discovered here. */
+#define PGM_FEATURE_CATEGORICAL 1 /* the *_cat entry points, pgm_param_layout_cat, pgm_uniform_noise */
 
 typedef void* pgm_stream_t; /* a hipStream_t (0 = the null stream) */
 
@@ -330,6 +348,65 @@ int pgm_randperm(int32_t n, int32_t count, uint64_t seed, int32_t* out, pgm_stre
 
 /* n standard-normal fp32 draws into out, element i keyed by (seed, i): the perf-mode noise stream. */
 int pgm_normal_noise(int64_t n, uint64_t seed, float* out, pgm_stream_t stream);
+
+/* ---- Discrete-action policies (pgm_abi_features() & PGM_FEATURE_CATEGORICAL).  The policy head is the reference's
+ * Categorical (model.py:33-35, distributions.py:54-68): logits z = Linear(actor features), one integer action per
+ * step.  In these entry points pgm_dims.A is the NUMBER OF ACTIONS; the stored action has width 1.  Environments are
+ * host-stepped (pgm_env_ingest accepts the categorical dim sets; it never reads the action).  Built for
+ * (O, A, K) = (3, 4, 2) (Deep Sea Treasure); pgm_dims.LN must be 0 (LayerNorm towers with a Categorical head are not
+ * built: PGM_E_UNSUPPORTED).  Every entry point validates before any device work: NULL pointers, check of the dims,
+ * the dim set, the step index or E, LN.
+ *
+ * SAMPLING RULE (device and test reference alike).  With fp32 logits z[0..A), m = max_j z_j, e_j = exp(z_j - m),
+ * s = e_0 + ... + e_{A-1} (index order), p_j = e_j / s and one uniform u in [0, 1) per (step, env):
+ *     action = #{ j < A-1 : p_0 + ... + p_j <= u }      (the partial sums in index order)
+ * so the action is always in [0, A); logp = z_a - (m + log s).  Deterministic: the lowest index among the maxima of
+ * z (FixedCategorical.mode = probs.argmax, distributions.py:27).  torch draws Categorical.sample through multinomial,
+ * whose stream is not reproduced: the rule is equal in distribution, not in draws.
+ *
+ * Storage: rb->actions is [P][T][N][1] fp32 holding the action index (exact; the reference's width-1 action tensor,
+ * storage.py:19-25); every other buffer as for the Gaussian head. */
+int pgm_abi_features(void); /* bit mask of PGM_FEATURE_*; a library without this symbol has none */
+
+/* offsets[PGM_NUM_PARAM_TENSORS_CAT] (floats; indices 0..9 in PGM_P_* order, then PGM_PC_LINEAR_W / _B), every tensor
+ * 16-byte aligned, *total a multiple of 64 floats. */
+int pgm_param_layout_cat(int32_t O, int32_t A, int32_t K, int32_t H, int32_t* offsets, int32_t* total);
+
+/* Policy.act on obs [P][N][O] (model.py:57-69 with dist = Categorical).  uniforms [N] (shared by tasks) draws by the
+ * sampling rule; deterministic = 1 takes the mode (uniforms ignored, may be NULL).  Outputs value [P][N][K],
+ * action int32 [P][N], logp [P][N]. */
+int pgm_act_forward_cat(const pgm_dims* d, const float* params, const float* obs, const float* uniforms,
+                        int32_t deterministic, float* value, int32_t* action, float* logp, pgm_stream_t stream);
+
+/* pgm_rollout_act with a Categorical head (morl/mopg.py:105-108; t == T: get_value, :132-135).  Reads rb->obs[p][t].
+ * 0 <= t < T: writes rb->values[p][t], rb->actions[p][t] (the index as fp32), rb->logp[p][t] and the index into
+ * action_out int32 [P][N]; uniforms is the base of a [T][N] stream (slice t is read) and is required.  t == T: writes
+ * rb->values[p][T] only; uniforms and action_out may be NULL.  Other t: PGM_E_SHAPE. */
+int pgm_rollout_act_cat(const pgm_dims* d, const float* params, const pgm_rollout_buf* rb, int32_t t,
+                        const float* uniforms, int32_t* action_out, pgm_stream_t stream);
+
+/* pgm_eval_act with a Categorical head (morl/mopg.py:36-39): the same fp64 normalisation of raw_obs [P][E][O],
+ * 1 <= E <= 8, then the deterministic action into action_out int32 [P][E]. */
+int pgm_eval_act_cat(const pgm_dims* d, const float* params, const double* ob_mean, const double* ob_var,
+                     int32_t use_ob_rms, const double* raw_obs, int32_t E, int32_t* action_out, pgm_stream_t stream);
+
+/* PPO.update (a2c_ppo_acktr/algo/ppo.py:58-115) with FixedCategorical log_probs and entropy (model.py:75-82):
+ * arguments as pgm_ppo_update, params / adam_m / adam_v [P][L] in the pgm_param_layout_cat layout, rb->actions
+ * [P][T][N][1].  Per sample with taken action a: p = softmax(z), logp = log p_a, H = -sum_j p_j log p_j; the loss is
+ * the clipped surrogate on exp(logp - old logp), the (clipped) value loss and -entropy_coef mean(H).
+ * stats [P][3] = mean (value_loss, action_loss, entropy).  ppo_update_cat_kernel: one 256-thread workgroup per tower
+ * with the tower's parameters and Adam moments LDS-resident, the norm granules and timeout word (8-byte word 2P of the
+ * workspace) of pgm_ppo_update; needs 2 P <= CU count and all working workgroups co-resident (PGM_E_UNSUPPORTED
+ * otherwise: shard the tasks over more GPUs).  workspace: pgm_ppo_update_cat_workspace_bytes(d) caller-owned device
+ * bytes, reset inside the call on `stream`. */
+int pgm_ppo_update_cat(const pgm_dims* d, const pgm_ppo_hparams* hp, float* params, float* adam_m, float* adam_v,
+                       int32_t* adam_step, const float* lr, const int32_t* perms, const pgm_rollout_buf* rb,
+                       float* stats, void* workspace, pgm_stream_t stream);
+size_t pgm_ppo_update_cat_workspace_bytes(const pgm_dims* d); /* monotone in d->P */
+
+/* n uniform fp32 draws in [0, 1) with 24 random bits into out, element i keyed by (seed, i) through the counter hash
+ * of pgm_normal_noise: the perf-mode stream of the sampling rule. */
+int pgm_uniform_noise(int64_t n, uint64_t seed, float* out, pgm_stream_t stream);
 
 #ifdef __cplusplus
 }

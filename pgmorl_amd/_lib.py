@@ -23,6 +23,8 @@ PARAM_TENSORS = ['actor_w1', 'actor_b1', 'actor_w2', 'actor_b2', 'critic_w1', 'c
 PARAM_TENSORS_LN = ['actor_w1', 'actor_g1', 'actor_be1', 'actor_w2', 'actor_g2', 'actor_be2',
                     'critic_w1', 'critic_g1', 'critic_be1', 'critic_w2', 'critic_g2', 'critic_be2',
                     'value_w', 'value_b', 'mean_w', 'mean_b', 'logstd']
+# Categorical head (discrete actions): the ten tower / value tensors, then dist.linear (pgm_param_layout_cat)
+PARAM_TENSORS_CAT = PARAM_TENSORS[:10] + ['linear_w', 'linear_b']
 
 P_ = C.c_void_p
 I32 = C.c_int32
@@ -118,7 +120,24 @@ _SIGS = {
     'pgm_env_ingest': (C.c_int, [C.POINTER(Dims), C.POINTER(EnvState), C.POINTER(NormState), C.POINTER(RolloutBuf),
                                  I32, P_, P_, P_, P_, P_, P_]),
     'pgm_eval_act': (C.c_int, [C.POINTER(Dims), P_, P_, P_, I32, P_, I32, P_, P_]),
+    # discrete-action policies (pgm_abi_features() & FEATURE_CATEGORICAL)
+    'pgm_abi_features': (C.c_int, []),
+    'pgm_param_layout_cat': (C.c_int, [I32, I32, I32, I32, C.POINTER(I32), C.POINTER(I32)]),
+    'pgm_act_forward_cat': (C.c_int, [C.POINTER(Dims), P_, P_, P_, I32, P_, P_, P_, P_]),
+    'pgm_rollout_act_cat': (C.c_int, [C.POINTER(Dims), P_, C.POINTER(RolloutBuf), I32, P_, P_, P_]),
+    'pgm_eval_act_cat': (C.c_int, [C.POINTER(Dims), P_, P_, P_, I32, P_, I32, P_, P_]),
+    'pgm_ppo_update_cat': (C.c_int, [C.POINTER(Dims), C.POINTER(PPOHParams), P_, P_, P_, P_, P_, P_,
+                                     C.POINTER(RolloutBuf), P_, P_, P_]),
+    'pgm_ppo_update_cat_workspace_bytes': (C.c_size_t, [C.POINTER(Dims)]),
+    'pgm_uniform_noise': (C.c_int, [C.c_int64, C.c_uint64, P_, P_]),
 }
+# the symbols a library of the same ABI version and minor may lack: discovered through pgm_abi_features
+FEATURE_CATEGORICAL = 1
+_FEATURE_SYMBOLS = {'pgm_abi_features': 0, 'pgm_param_layout_cat': FEATURE_CATEGORICAL,
+                    'pgm_act_forward_cat': FEATURE_CATEGORICAL, 'pgm_rollout_act_cat': FEATURE_CATEGORICAL,
+                    'pgm_eval_act_cat': FEATURE_CATEGORICAL, 'pgm_ppo_update_cat': FEATURE_CATEGORICAL,
+                    'pgm_ppo_update_cat_workspace_bytes': FEATURE_CATEGORICAL,
+                    'pgm_uniform_noise': FEATURE_CATEGORICAL}
 
 EXPORTS = tuple(_SIGS)
 
@@ -136,6 +155,8 @@ def _load(path):
             raise PGMError(f'{path} not built; run `python -m pgmorl_amd.build` (hipcc, gfx950)')
         h = C.CDLL(path)
         for name, (res, args) in _SIGS.items():
+            if name in _FEATURE_SYMBOLS and not hasattr(h, name):
+                continue  # an older library of this ABI: features() reports what is missing
             f = getattr(h, name)
             f.restype, f.argtypes = res, args
         if h.pgm_abi_version() != PGM_ABI_VERSION:
@@ -174,6 +195,28 @@ def param_layout(O, A, K, H=64):
     tot = I32()
     check(lib().pgm_param_layout(O, A, K, H, offs, C.byref(tot)), 'pgm_param_layout')
     return dict(zip(PARAM_TENSORS, list(offs))), tot.value
+
+
+def features():
+    """pgm_abi_features(): the bit mask of optional entry-point groups; a library without the symbol has none."""
+    h = lib()
+    return int(h.pgm_abi_features()) if hasattr(h, 'pgm_abi_features') else 0
+
+
+def require_categorical():
+    if not features() & FEATURE_CATEGORICAL:
+        raise PGMError('this libpgm.so has no Categorical-head entry points (pgm_abi_features() & 1 is clear); '
+                       'rebuild it with `python -m pgmorl_amd.build`')
+
+
+def param_layout_cat(O, A, K, H=64):
+    """(offsets dict, total) of the flat per-task parameter vector of a Categorical-head policy, A = number of
+    actions (pgm_param_layout_cat)."""
+    require_categorical()
+    offs = (I32 * len(PARAM_TENSORS_CAT))()
+    tot = I32()
+    check(lib().pgm_param_layout_cat(O, A, K, H, offs, C.byref(tot)), 'pgm_param_layout_cat')
+    return dict(zip(PARAM_TENSORS_CAT, list(offs))), tot.value
 
 
 def param_layout_ln(O, A, K, H=64):

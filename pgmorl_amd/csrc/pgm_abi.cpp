@@ -121,6 +121,22 @@ LayoutLN make_layout_ln(int O, int A, int K, int Hd) {
     return L;
 }
 
+LayoutCat make_layout_cat(int O, int A, int K, int Hd) {
+    const int32_t sizes[PGM_NUM_PARAM_TENSORS_CAT] = {
+        O * Hd, Hd, Hd * Hd, Hd,   // actor tower
+        O * Hd, Hd, Hd * Hd, Hd,   // critic tower
+        Hd * K, K,                 // critic_linear
+        Hd * A, A};                // dist.linear (A = number of actions)
+    LayoutCat L;
+    int32_t p = 0;
+    for (int i = 0; i < PGM_NUM_PARAM_TENSORS_CAT; ++i) {
+        L.off[i] = p;
+        p = round_up(p + sizes[i], 4);  // 16-byte aligned tensors
+    }
+    L.total = round_up(p, 64);
+    return L;
+}
+
 }  // namespace pgm
 
 extern "C" {
@@ -128,6 +144,19 @@ extern "C" {
 int pgm_abi_version(void) { return PGM_ABI_VERSION; }
 
 int pgm_abi_minor(void) { return PGM_ABI_MINOR; }
+
+int pgm_abi_features(void) { return PGM_FEATURE_CATEGORICAL; }
+
+int pgm_param_layout_cat(int32_t O, int32_t A, int32_t K, int32_t H, int32_t* offsets, int32_t* total) {
+    if (O <= 0 || A <= 0 || K <= 0 || H <= 0 || !offsets || !total) {
+        pgm::set_error("pgm_param_layout_cat: bad arguments");
+        return PGM_E_INVALID_ARG;
+    }
+    pgm::LayoutCat L = pgm::make_layout_cat(O, A, K, H);
+    for (int i = 0; i < PGM_NUM_PARAM_TENSORS_CAT; ++i) offsets[i] = L.off[i];
+    *total = L.total;
+    return PGM_OK;
+}
 
 const char* pgm_last_error(void) { return pgm::g_err; }
 

@@ -27,6 +27,12 @@ struct LayoutLN {
     int32_t total;
 };
 LayoutLN make_layout_ln(int O, int A, int K, int Hd);
+// Categorical head (discrete actions): the 12 tensors of pgm_param_layout_cat, A = number of actions
+struct LayoutCat {
+    int32_t off[PGM_NUM_PARAM_TENSORS_CAT];
+    int32_t total;
+};
+LayoutCat make_layout_cat(int O, int A, int K, int Hd);
 // pgm_ppo_update workspace: [2 PGM_NS_MAX P + 1] tagged 8-byte granules (tower-norm hand-offs of every
 // (task, tower, row part); word 2P = timeout flag), padded to 256 bytes; the gradient exchange of the
 // row-split updates, [P][2 towers][PGM_NS_MAX row parts][2 parities] slots of (tower image + 1) granules; then

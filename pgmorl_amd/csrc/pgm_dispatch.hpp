@@ -24,6 +24,29 @@ int dispatch_dims(int O, int A, int K, const char* what, F&& f) {
     return PGM_E_UNSUPPORTED;
 }
 
+// (O, A, K) of the discrete-action envs (Categorical head; A = number of actions): Deep Sea Treasure.  One X(...) per
+// dim set; the *_cat entry points and pgm_env_ingest instantiate their kernels for each.
+#define PGM_CAT_DIMS(X) X(3, 4, 2)
+inline bool is_cat_dims(int O, int A, int K) {
+#define PGM_X(o, a, k) if (O == o && A == a && K == k) return true;
+    PGM_CAT_DIMS(PGM_X)
+#undef PGM_X
+    return false;
+}
+template <class F>
+int dispatch_dims_cat(int O, int A, int K, const char* what, F&& f) {
+#define PGM_X(o, a, k) if (O == o && A == a && K == k) return f(ic<o>{}, ic<a>{}, ic<k>{});
+    PGM_CAT_DIMS(PGM_X)
+#undef PGM_X
+#define PGM_STR_(x) #x
+#define PGM_X(o, a, k) " " PGM_STR_(o) "/" PGM_STR_(a) "/" PGM_STR_(k)
+    set_error("%s: unsupported dims O=%d A=%d K=%d for a Categorical head (supported, A = number of actions:" PGM_CAT_DIMS(
+                  PGM_X) ")", what, O, A, K);
+#undef PGM_X
+#undef PGM_STR_
+    return PGM_E_UNSUPPORTED;
+}
+
 inline int check_dims(const pgm_dims* d, const char* what) {
     if (!d) {
         set_error("%s: null dims", what);
@@ -55,6 +78,20 @@ inline int check_ln(const pgm_dims* d, const char* what) {
         set_error("%s: LayerNorm towers are built for obs_dim <= 32 (17/6/2, 11/3/2, 11/3/3, 27/8/2, 8/2/2); obs_dim %d "
                   "(MO-Humanoid) needs a streamed layer-1 LayerNorm kernel that does not exist", what, d->O);
         return PGM_E_UNSUPPORTED;
+    }
+    return PGM_OK;
+}
+
+// Categorical entry points, after check_dims: the dim set ...
+inline int check_cat_dims(const pgm_dims* d, const char* what) {
+    return dispatch_dims_cat(d->O, d->A, d->K, what, [](auto, auto, auto) { return (int)PGM_OK; });
+}
+// ... and, last, pgm_dims.LN: no LayerNorm kernel has a Categorical head
+inline int check_cat_ln(const pgm_dims* d, const char* what) {
+    if (d->LN != 0) {
+        set_error("%s: pgm_dims.LN = %d: LayerNorm towers with a Categorical head are not built (LN must be 0)", what,
+                  d->LN);
+        return d->LN == 1 ? PGM_E_UNSUPPORTED : PGM_E_INVALID_ARG;
     }
     return PGM_OK;
 }

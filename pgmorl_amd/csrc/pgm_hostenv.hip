@@ -372,11 +372,14 @@ int pgm_env_ingest(const pgm_dims* d, const pgm_env_state* st, const pgm_norm_st
         return PGM_E_INVALID_ARG;
     }
     IngestArgs a{d->P, d->N, d->T, t, *st, *ns, *rb, raw_obs, raw_obj, reward, done, bad_transition};
-    return dispatch_dims(d->O, d->A, d->K, "pgm_env_ingest", [&](auto o, auto aa, auto k) {
+    auto launch = [&](auto o, auto aa, auto k) {
         constexpr int O = decltype(o)::value, A = decltype(aa)::value, K = decltype(k)::value;
         return launch_smem(env_ingest_kernel<O, A, K>, d->P, sizeof(StepSmem<O, A, K>), (hipStream_t)stream, a,
                            "pgm_env_ingest");
-    });
+    };
+    // the ingest never reads the action: the discrete-action dim sets (A = number of actions) share the kernel
+    if (is_cat_dims(d->O, d->A, d->K)) return dispatch_dims_cat(d->O, d->A, d->K, "pgm_env_ingest", launch);
+    return dispatch_dims(d->O, d->A, d->K, "pgm_env_ingest", launch);
 }
 
 int pgm_eval_act(const pgm_dims* d, const float* params, const double* ob_mean, const double* ob_var,

@@ -59,10 +59,27 @@ def env_names():
     return sorted(_ENVS)
 
 
+# Discrete-action envs: env id -> (obs_dim, number of actions, obj_num, max_episode_steps).  They have no SynthMO
+# stand-in and no device env: they are host-stepped (hostenv.DeepSeaTreasureHostVecEnv) and their policies carry the
+# reference's Categorical head (a2c_ppo_acktr/model.py:33-35).
+_DISCRETE_ENVS = {
+    'MO-DeepSeaTreasure-v0': (3, 4, 2, 50),
+}
+
+
+def discrete_env_names():
+    return sorted(_DISCRETE_ENVS)
+
+
 def make_spec(env_name):
-    """Constant arrays of one SynthMO env (all fp64)."""
+    """Constant arrays of one SynthMO env (all fp64); for a discrete-action env the dims alone, with
+    ``discrete = True`` and ``act_dim`` the number of actions."""
+    if env_name in _DISCRETE_ENVS:
+        O, A, K, tmax = _DISCRETE_ENVS[env_name]
+        return {'name': env_name, 'obs_dim': O, 'act_dim': A, 'obj_num': K, 'max_episode_steps': tmax,
+                'discrete': True}
     if env_name not in _ENVS:
-        raise ValueError(f'unknown env {env_name!r}; known: {env_names()}')
+        raise ValueError(f'unknown env {env_name!r}; known: {env_names() + discrete_env_names()}')
     O, A, K, tmax, (lo, hi), objrows = _ENVS[env_name]
     u = _uniforms(SPEC_SEED, O + O * A + O + K * O)
     p = 0

@@ -7,6 +7,8 @@ environments behind one ``step``: what the reference's per-task ``DummyVecEnv`` 
 fp64 observations, the scalar env reward, ``info['obj']`` and the done / bad_transition flags.
 
 * ``SynthHostVecEnv``  SynthMO (envspec.py) in numpy fp64: the stand-in that exercises the whole path without MuJoCo.
+* ``DeepSeaTreasureHostVecEnv``  Deep Sea Treasure (``--host-env dst``), the discrete-action grid world of the reference's
+                       shipped run, vectorised numpy.
 * ``GymHostVecEnv``    any ``make_env(env_name, seed, rank)`` returning gym-style objects (duck-typed: gym itself is
                        never imported here), in the 4-tuple or the 5-tuple step API.
 """
@@ -23,8 +25,12 @@ MAX_WORKERS = 16  # cap of GymHostVecEnv's optional thread pool (never sized fro
 class HostVecEnv:
     """The protocol ``TaskBatch`` drives.  Attributes: ``P`` (active tasks), ``N`` (envs per task), ``obs_dim``,
     ``act_dim``, ``obj_num``.  Every task's env n is seeded ``seed + n`` (each task process of the reference builds
-    its own ``make_vec_envs(env_name, seed, N)``, morl/mopg.py:67-69)."""
+    its own ``make_vec_envs(env_name, seed, N)``, morl/mopg.py:67-69).
+
+    ``discrete = True``: a Discrete(n) action space.  ``act_dim`` is then the number of actions n and ``step`` /
+    ``eval_step`` receive the action indices as int32 [P, N] / [P, E] (the policy has the Categorical head)."""
     P = N = obs_dim = act_dim = obj_num = 0
+    discrete = False
 
     def set_active(self, P):
         """Use the first P tasks (P <= the P of construction); followed by ``reset()``."""
@@ -65,6 +71,8 @@ class SynthHostVecEnv(HostVecEnv):
 
     def __init__(self, env_name, P, N, seed=0, max_episode_steps=None):
         sp = envspec.make_spec(env_name)
+        if sp.get('discrete'):
+            raise ValueError(f'{env_name} has discrete actions and no SynthMO stand-in (use --host-env dst)')
         self.spec = sp
         self.env_name, self.seed = env_name, seed
         self.capacity = self.P = P
@@ -123,6 +131,96 @@ class SynthHostVecEnv(HostVecEnv):
         return self._es.copy(), obj, done
 
 
+class DeepSeaTreasureHostVecEnv(HostVecEnv):
+    """Deep Sea Treasure (MO-DeepSeaTreasure-v0: obs 3, Discrete(4), 2 objectives), P x N grids in numpy.
+
+    An 11 x 11 grid; cell (r, c) is water if r == 0 or r <= c, otherwise wall; the treasure cells (1,0) = 1,
+    (2,1) = 3, (4,3) = 8, (7,6) = 20 can be entered.  An episode starts at (0, 0).  Actions 0 up, 1 down, 2 left,
+    3 right; a move into a wall or off the grid leaves the position unchanged.  Every step t += 1; on a treasure cell
+    reward = obj_0 = its value and obj_1 = 10 / (t + 1), otherwise all three are 0.  The episode ends on a treasure or
+    at t == max_steps.  The raw observation is [r / 10, c / 10, t / max_steps], rounded to fp32 (the env's dtype) and
+    widened.  The step limit is reported as a termination (bad = False), as the env itself reports it;
+    ``time_limit_is_bad=True`` reports it as a time-limit end instead (tests: both kinds of episode end)."""
+    discrete = True
+    SIZE = 11
+    TREASURES = {(1, 0): 1.0, (2, 1): 3.0, (4, 3): 8.0, (7, 6): 20.0}
+    _DR = np.array([-1, 1, 0, 0])
+    _DC = np.array([0, 0, -1, 1])
+
+    def __init__(self, env_name='MO-DeepSeaTreasure-v0', P=1, N=1, seed=0, max_steps=None, time_limit_is_bad=False):
+        sp = envspec.make_spec(env_name)
+        if not sp.get('discrete') or (sp['obs_dim'], sp['act_dim'], sp['obj_num']) != (3, 4, 2):
+            raise ValueError(f'{env_name} is not a Deep Sea Treasure env (obs 3, 4 actions, 2 objectives)')
+        self.env_name, self.seed = env_name, seed  # (the env draws nothing: every seed gives the same episodes)
+        self.capacity = self.P = P
+        self.N = N
+        self.obs_dim, self.act_dim, self.obj_num = sp['obs_dim'], sp['act_dim'], sp['obj_num']
+        self.max_steps = int(max_steps or sp['max_episode_steps'])
+        self.time_limit_is_bad = bool(time_limit_is_bad)
+        n = self.SIZE
+        r, c = np.mgrid[0:n, 0:n]
+        self.value = np.zeros((n, n))
+        for cell, v in self.TREASURES.items():
+            self.value[cell] = v
+        self.open = (r == 0) | (r <= c) | (self.value > 0)
+        self._st = self._est = None  # (row, col, t) int64 [P, N] / [P, E]
+        self._edone = None
+
+    def set_active(self, P):
+        if not 0 < P <= self.capacity:
+            raise ValueError(f'active tasks {P} outside [1, {self.capacity}]')
+        self.P = P
+        self._st = None
+
+    def _obs(self, st):
+        r, c, t = st
+        o = np.stack([r / (self.SIZE - 1), c / (self.SIZE - 1), t / self.max_steps], axis=-1)
+        return o.astype(np.float32).astype(np.float64)
+
+    def _move(self, st, actions, frozen=None):
+        """One step of every env not in ``frozen`` -> (treasure value, fuel objective, found, at the step limit)."""
+        r, c, t = st
+        a = np.asarray(actions).astype(np.int64)
+        a = np.where((a >= 0) & (a < 4), a, 0)
+        nr, nc = r + self._DR[a], c + self._DC[a]
+        n = self.SIZE
+        ok = (nr >= 0) & (nr < n) & (nc >= 0) & (nc < n)
+        ok &= self.open[np.clip(nr, 0, n - 1), np.clip(nc, 0, n - 1)]
+        if frozen is not None:
+            ok &= ~frozen
+        r[...] = np.where(ok, nr, r)
+        c[...] = np.where(ok, nc, c)
+        t += 1 if frozen is None else (~frozen).astype(np.int64)
+        val = self.value[r, c]
+        found = val > 0
+        if frozen is not None:
+            val, found = np.where(frozen, 0.0, val), found & ~frozen
+        fuel = np.where(found, 10.0 / (t + 1), 0.0)
+        return val, fuel, found, t >= self.max_steps
+
+    def reset(self):
+        self._st = tuple(np.zeros((self.P, self.N), dtype=np.int64) for _ in range(3))
+        return self._obs(self._st)
+
+    def step(self, actions):
+        val, fuel, found, limit = self._move(self._st, actions)
+        done = found | limit
+        bad = limit & ~found if self.time_limit_is_bad else np.zeros_like(done)
+        for x in self._st:  # DummyVecEnv auto-reset: the returned observation is the next episode's first
+            x[done] = 0
+        return self._obs(self._st), val.copy(), done, bad, np.stack([val, fuel], axis=-1)
+
+    def eval_reset(self, eval_num):
+        self._est = tuple(np.zeros((self.P, eval_num), dtype=np.int64) for _ in range(3))
+        self._edone = np.zeros((self.P, eval_num), dtype=bool)
+        return self._obs(self._est)
+
+    def eval_step(self, actions):
+        val, fuel, found, limit = self._move(self._est, actions, frozen=self._edone)  # ended episodes stand still
+        self._edone = self._edone | found | limit
+        return self._obs(self._est), np.stack([val, fuel], axis=-1), self._edone.copy()
+
+
 def _reset_obs(r):
     """env.reset(): obs (old API) or (obs, info) (new API)."""
     if isinstance(r, tuple) and len(r) == 2 and isinstance(r[1], dict):
@@ -144,14 +242,21 @@ def _step_env(env, action):
             np.asarray(info['obj'], dtype=np.float64).reshape(-1))
 
 
+def is_discrete(space):
+    """A gym-style action space with an ``n`` attribute is Discrete(n)."""
+    return hasattr(space, 'n')
+
+
 def probe_dims(env):
-    """(obs_dim, act_dim, obj_num) of one gym-style multi-objective env (resets it; may step it once)."""
+    """(obs_dim, act_dim, obj_num) of one gym-style multi-objective env (resets it; may step it once).  For a
+    discrete action space act_dim is its number of actions n."""
     obs = _reset_obs(env.reset())
-    act_dim = int(np.prod(env.action_space.shape))
+    disc = is_discrete(env.action_space)
+    act_dim = int(env.action_space.n) if disc else int(np.prod(env.action_space.shape))
     inner = getattr(env, 'unwrapped', env)
     obj_num = getattr(inner, 'obj_dim', None)
     if obj_num is None:
-        obj_num = _step_env(env, np.zeros(act_dim, dtype=np.float32))[4].size
+        obj_num = _step_env(env, 0 if disc else np.zeros(act_dim, dtype=np.float32))[4].size
         env.reset()
     return obs.size, act_dim, int(obj_num)
 
@@ -167,6 +272,7 @@ class GymHostVecEnv(HostVecEnv):
         self.N = N
         self.envs = [[make_env(env_name, seed, n) for n in range(N)] for _ in range(P)]
         self.obs_dim, self.act_dim, self.obj_num = probe_dims(self.envs[0][0])
+        self.discrete = is_discrete(self.envs[0][0].action_space)  # then step passes Python ints
         self._eval = []
         workers = min(MAX_WORKERS, int(workers), P * N)
         self._pool = ThreadPoolExecutor(max_workers=workers) if workers > 1 else None
@@ -186,7 +292,8 @@ class GymHostVecEnv(HostVecEnv):
 
     def step(self, actions):
         actions = np.asarray(actions)
-        jobs = [(self.envs[p][n], actions[p, n]) for p in range(self.P) for n in range(self.N)]
+        act = (lambda p, n: int(actions[p, n])) if self.discrete else (lambda p, n: actions[p, n])
+        jobs = [(self.envs[p][n], act(p, n)) for p in range(self.P) for n in range(self.N)]
 
         def one(job):
             env, a = job
@@ -225,7 +332,8 @@ class GymHostVecEnv(HostVecEnv):
             for e in range(E):
                 if self._eval_done[p, e]:  # an ended episode is not stepped again
                     continue
-                o, _, done, _, ob = _step_env(self._eval[p][e], actions[p, e])
+                a = int(actions[p, e]) if self.discrete else actions[p, e]
+                o, _, done, _, ob = _step_env(self._eval[p][e], a)
                 self._eval_obs[p, e], obj[p, e], self._eval_done[p, e] = o, ob, done
         return self._eval_obs.copy(), obj, self._eval_done.copy()
 
@@ -241,14 +349,16 @@ class GymHostVecEnv(HostVecEnv):
 
 
 def resolve(spec):
-    """``--host-env SPEC`` -> factory(env_name, P, N, seed) of a HostVecEnv.  ``synth``: SynthHostVecEnv;
-    ``module:callable``: GymHostVecEnv over ``callable(env_name, seed, rank)``.  Raises ValueError for a spec that
+    """``--host-env SPEC`` -> factory(env_name, P, N, seed) of a HostVecEnv.  ``synth``: SynthHostVecEnv; ``dst``:
+    DeepSeaTreasureHostVecEnv; ``module:callable``: GymHostVecEnv over ``callable(env_name, seed, rank)``.  Raises ValueError for a spec that
     cannot be imported."""
     if spec == 'synth':
         return SynthHostVecEnv
+    if spec == 'dst':
+        return DeepSeaTreasureHostVecEnv
     mod, sep, name = str(spec).partition(':')
     if not sep or not mod or not name:
-        raise ValueError(f'--host-env {spec!r}: expected "synth" or "module:callable"')
+        raise ValueError(f'--host-env {spec!r}: expected "synth", "dst" or "module:callable"')
     try:
         fn = getattr(importlib.import_module(mod), name)
     except (ImportError, AttributeError) as e:

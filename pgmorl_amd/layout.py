@@ -4,12 +4,13 @@ The device stores every weight TRANSPOSED ([in][out], so a lane per output unit 
 consecutive addresses) in the reference's named_parameters() order, each tensor 16-byte aligned
 (offsets from pgm_param_layout, include/pgm_abi.h).  State-dict keys are the reference's
 (a2c_ppo_acktr/model.py:211-254, a2c_ppo_acktr/distributions.py:78-79): STATE_KEYS for layernorm=False,
-STATE_KEYS_LN (Linear(bias=False) -> LayerNorm -> tanh towers, 17 tensors, pgm_param_layout_ln) for layernorm=True.
+STATE_KEYS_LN (Linear(bias=False) -> LayerNorm -> tanh towers, 17 tensors, pgm_param_layout_ln) for layernorm=True,
+STATE_KEYS_CAT (the Categorical head of a Discrete action space, 12 tensors, pgm_param_layout_cat) for discrete=True.
 """
 import numpy as np
 import torch
 
-from ._lib import param_layout, param_layout_ln
+from ._lib import param_layout, param_layout_cat, param_layout_ln
 
 # (state_dict key, device tensor name, transposed on device)
 STATE_KEYS = [
@@ -52,11 +53,27 @@ STATE_KEYS_LN = [
 ]
 
 
-def state_keys(layernorm=False):
+# discrete=True: a Discrete(n) action space gets the reference's Categorical head (a2c_ppo_acktr/model.py:33-35,
+# distributions.py:54-68): the ten tower / value tensors, then dist.linear; no logstd
+STATE_KEYS_CAT = STATE_KEYS[:10] + [
+    ('dist.linear.weight', 'linear_w', True),
+    ('dist.linear.bias', 'linear_b', False),
+]
+
+
+def state_keys(layernorm=False, discrete=False):
+    if discrete:
+        if layernorm:
+            raise ValueError('layernorm=True with discrete=True: LayerNorm towers with a Categorical head are not built')
+        return STATE_KEYS_CAT
     return STATE_KEYS_LN if layernorm else STATE_KEYS
 
 
-def ref_shapes(O, A, K, H=64, layernorm=False):
+def ref_shapes(O, A, K, H=64, layernorm=False, discrete=False):
+    if discrete:  # A = number of actions
+        sh = {k: v for k, v in ref_shapes(O, A, K, H).items() if not k.startswith('dist.')}
+        sh.update({'dist.linear.weight': (A, H), 'dist.linear.bias': (A,)})
+        return sh
     if layernorm:
         sh = {}
         for tw in ('actor', 'critic'):
@@ -75,12 +92,14 @@ def ref_shapes(O, A, K, H=64, layernorm=False):
 
 
 class ParamLayout:
-    def __init__(self, O, A, K, H=64, layernorm=False):
+    def __init__(self, O, A, K, H=64, layernorm=False, discrete=False):
         self.O, self.A, self.K, self.H = O, A, K, H
-        self.layernorm = bool(layernorm)
-        self.keys = state_keys(self.layernorm)  # (state_dict key, device tensor, transposed), parameter order
-        self.offsets, self.total = (param_layout_ln if self.layernorm else param_layout)(O, A, K, H)
-        self.shapes = ref_shapes(O, A, K, H, self.layernorm)
+        self.layernorm, self.discrete = bool(layernorm), bool(discrete)
+        # (state_dict key, device tensor, transposed), parameter order
+        self.keys = state_keys(self.layernorm, self.discrete)
+        fn = param_layout_cat if self.discrete else param_layout_ln if self.layernorm else param_layout
+        self.offsets, self.total = fn(O, A, K, H)
+        self.shapes = ref_shapes(O, A, K, H, self.layernorm, self.discrete)
 
     def flatten(self, tensors, dtype=np.float32):
         """Reference-shaped tensors (dict key -> array-like, e.g. a state_dict) -> flat [total] array."""

@@ -32,6 +32,16 @@ def host_draws(j, T, N, A, E):
     return z.float(), perms.to(torch.int32)
 
 
+def host_draws_discrete(j, T, N, E):
+    """The host stream of a Categorical head: after torch.manual_seed(j), one torch.rand(N) per step for the
+    sampling rule of include/pgm_abi.h, then the randperms.  torch draws Categorical.sample through multinomial,
+    whose stream is not reproduced: equal in distribution to the reference, not in draws."""
+    torch.manual_seed(j)
+    u = torch.stack([torch.rand(N, dtype=torch.float32) for _ in range(T)])
+    perms = torch.stack([torch.randperm(T * N) for _ in range(E)])
+    return u, perms.to(torch.int32)
+
+
 def linear_lr(j, total_num_updates, lr, ratio=1.0):
     """update_linear_schedule (a2c_ppo_acktr/utils.py:46-50) as called at morl/mopg.py:97-101."""
     return lr - lr * (j * ratio / float(total_num_updates))
@@ -63,7 +73,8 @@ class MOPGPopulation:
             return self.tb.layout
         spec = make_spec(self.args.env_name)
         return ParamLayout(spec['obs_dim'], spec['act_dim'], spec['obj_num'],
-                           layernorm=bool(getattr(self.args, 'layernorm', False)))
+                           layernorm=bool(getattr(self.args, 'layernorm', False)),
+                           discrete=bool(spec.get('discrete', False)))
 
     def _batch(self, P):
         """The one TaskBatch of this runtime, P active task slots.  Allocated once (re-allocated only when a
@@ -220,7 +231,9 @@ class MOPGPopulation:
             for i, j in enumerate(its):
                 lr = linear_lr(j, total, a.lr, a.lr_decay_ratio) if a.use_linear_lr_decay else a.lr
                 noise = perms = None
-                if self.rng == 'host':
+                if self.rng == 'host' and tb.discrete:
+                    noise, perms = host_draws_discrete(j, a.num_steps, a.num_processes, a.ppo_epoch)
+                elif self.rng == 'host':
                     noise, perms = host_draws(j, a.num_steps, a.num_processes, tb.A, a.ppo_epoch)
                 tb.iteration(j, lr, noise=noise, perms=perms, carry=i > 0, overlap_eval=True, objs_out=objs_ar[i])
                 arena[i].copy_(tb.state)

@@ -40,7 +40,8 @@ def initialize_warm_up_batch(args, runtime):
     dev = runtime.device
     for w in weights_batch:
         pol = new_policy(spec['obs_dim'], spec['act_dim'], args.obj_num,
-                         layernorm=bool(getattr(args, 'layernorm', False)))
+                         layernorm=bool(getattr(args, 'layernorm', False)),
+                         discrete=bool(spec.get('discrete', False)))
         flat = torch.from_numpy(layout.flatten(pol.state_dict())).to(dev)
         snap = DeviceSnapshot(layout, flat, torch.zeros_like(flat), torch.zeros_like(flat), 0)
         env_params = {'ob_rms': RunningMeanStd(shape=(spec['obs_dim'],)) if args.ob_rms else None,

@@ -34,6 +34,16 @@ class _Gaussian(nn.Module):
         self.logstd = _AddBias(act_dim)
 
 
+class _Categorical(nn.Module):
+    """The head of a Discrete(n) action space (distributions.py:54-68): one Linear, orthogonal gain 0.01, zero bias."""
+
+    def __init__(self, hidden, num_actions):
+        super().__init__()
+        self.linear = nn.Linear(hidden, num_actions)
+        nn.init.orthogonal_(self.linear.weight.data, gain=0.01)
+        nn.init.constant_(self.linear.bias.data, 0.0)
+
+
 class _Base(nn.Module):
     def __init__(self, obs_dim, obj_num, hidden, layernorm=False):
         super().__init__()
@@ -62,16 +72,17 @@ class _Base(nn.Module):
 class Policy(nn.Module):
     """Parameter container with the reference's module tree / state_dict keys."""
 
-    def __init__(self, obs_dim, act_dim, obj_num, hidden=64, layernorm=False):
+    def __init__(self, obs_dim, act_dim, obj_num, hidden=64, layernorm=False, discrete=False):
         super().__init__()
         self.base = _Base(obs_dim, obj_num, hidden, layernorm)
-        self.dist = _Gaussian(hidden, act_dim)
+        # model.py:33-38: the head follows the action space; discrete: act_dim is the number of actions
+        self.dist = _Categorical(hidden, act_dim) if discrete else _Gaussian(hidden, act_dim)
 
 
-def new_policy(obs_dim, act_dim, obj_num, hidden=64, layernorm=False):
+def new_policy(obs_dim, act_dim, obj_num, hidden=64, layernorm=False, discrete=False):
     prev = torch.get_default_dtype()
     torch.set_default_dtype(torch.float64)
     try:
-        return Policy(obs_dim, act_dim, obj_num, hidden, layernorm).double()
+        return Policy(obs_dim, act_dim, obj_num, hidden, layernorm, discrete).double()
     finally:
         torch.set_default_dtype(prev)

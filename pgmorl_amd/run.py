@@ -106,6 +106,14 @@ def main(argv=None):
             raise PGMError(f'--layernorm with {args.env_name}: the LayerNorm kernels keep layer 1 LDS-resident and '
                            f'are built for obs_dim <= {LN_MAX_OBS}; obs_dim {obs_dim} would need a streamed layer-1 '
                            f'LayerNorm kernel, which does not exist')
+    from .envspec import discrete_env_names
+    if args.env_name in discrete_env_names():  # refused here too: no device env and no LayerNorm kernel for them
+        from ._lib import PGMError
+        if args.host_env is None:
+            raise PGMError(f'{args.env_name} has discrete actions and no device environment: it runs host-stepped, '
+                           f'pass --host-env (dst: the built-in Deep Sea Treasure, or module:callable)')
+        if args.layernorm:
+            raise PGMError(f'--layernorm with {args.env_name}: LayerNorm towers with a Categorical head are not built')
     if args.host_env is not None:  # refused here too: a spec that cannot be imported or whose env dims differ
         from ._lib import PGMError
         from .hostenv import check_spec

@@ -21,7 +21,8 @@ import numpy as np
 import torch
 
 from . import envspec
-from ._lib import (Dims, EnvSpec, EnvState, NormState, PGMError, PPOHParams, RolloutBuf, check, launch_opts, lib)
+from ._lib import (Dims, EnvSpec, EnvState, NormState, PGMError, PPOHParams, RolloutBuf, check, launch_opts, lib,
+                   require_categorical)
 from .layout import ParamLayout
 
 F32, F64, I32 = torch.float32, torch.float64, torch.int32
@@ -76,7 +77,18 @@ class TaskBatch:
             raise PGMError(f'layernorm=True with {env_name}: the LayerNorm kernels keep layer 1 LDS-resident and are '
                            f'built for obs_dim <= {LN_MAX_OBS}; obs_dim {self.O} would need a streamed layer-1 '
                            f'LayerNorm kernel, which does not exist')
-        self.layout = ParamLayout(self.O, self.A, self.K, self.H, layernorm=self.layernorm)
+        # a discrete-action env (spec['discrete']): Categorical head, A = number of actions, one width-1 action per
+        # step, the *_cat entry points; such envs exist on the host only
+        self.discrete = bool(sp.get('discrete', False))
+        if self.discrete:
+            if host_env is None:
+                raise PGMError(f'{env_name} has discrete actions and no device environment: TaskBatch needs '
+                               f'host_env=... (hostenv.DeepSeaTreasureHostVecEnv, --host-env dst)')
+            if self.layernorm:
+                raise PGMError(f'layernorm=True with {env_name}: LayerNorm towers with a Categorical head are not built')
+            require_categorical()
+        self.act_width = 1 if self.discrete else self.A
+        self.layout = ParamLayout(self.O, self.A, self.K, self.H, layernorm=self.layernorm, discrete=self.discrete)
         L, O, A, K, N, T = self.layout.total, self.O, self.A, self.K, self.N, self.T
         self._full = {}  # name -> full-capacity tensor whose leading dim is the task slot
 
@@ -86,7 +98,7 @@ class TaskBatch:
             return t
         # spec constants + reset tables (fp64)
         self._spec_t = {k: torch.tensor(np.ascontiguousarray(sp[k]), dtype=F64, device=self.dev)
-                        for k in ('d', 'U', 'c', 'V', 'ebase', 'ecoef', 'act_lo', 'act_hi')}
+                        for k in ('d', 'U', 'c', 'V', 'ebase', 'ecoef', 'act_lo', 'act_hi') if k in sp}
         self.s0_train = torch.tensor(envspec.reset_table(O, seed, N), dtype=F64, device=self.dev)
         self.s0_eval = torch.tensor(envspec.reset_table(O, seed, eval_num), dtype=F64, device=self.dev)
         # policy + optimiser: one [3][Pc][L] region
@@ -109,7 +121,7 @@ class TaskBatch:
         z('ret', N, dt=F64)
         # rollout storage (storage.py:12-30)
         z('obs', T + 1, N, O)
-        z('actions', T, N, A)
+        z('actions', T, N, self.act_width)
         z('logp', T, N)
         z('values', T + 1, N, K)
         z('returns', T + 1, N, K)
@@ -123,14 +135,16 @@ class TaskBatch:
         # segments ob_mean, ob_var (STAT_SEGMENTS order)
         self._eval_ob = torch.zeros(2, Pc, O, dtype=F64, device=self.dev)
         self.perms = torch.zeros(ppo_epoch, T * N, dtype=I32, device=self.dev)
-        self.noise = torch.zeros(T, N, A, dtype=F32, device=self.dev)
+        # the rollout's random stream: standard normals [T][N][A], or (discrete) one uniform per (step, env) [T][N]
+        self.noise = torch.zeros((T, N) if self.discrete else (T, N, A), dtype=F32, device=self.dev)
         self.hp = PPOHParams(clip_param=clip_param, value_loss_coef=value_loss_coef, entropy_coef=entropy_coef,
                              max_grad_norm=max_grad_norm, adam_eps=adam_eps, beta1=0.9, beta2=0.999,
                              ppo_epoch=ppo_epoch, num_mini_batch=num_mini_batch,
                              use_clipped_value_loss=int(use_clipped_value_loss))
         self._eval_stream, self._eval_done = None, None
         self._reset_pending = False  # a pgm_ppo_update_reset queued on the side stream, not yet waited for
-        nws = lib().pgm_ppo_update_workspace_bytes(C.byref(Dims(Pc, N, T, O, A, K, self.H, int(self.layernorm))))
+        ws_bytes = lib().pgm_ppo_update_cat_workspace_bytes if self.discrete else lib().pgm_ppo_update_workspace_bytes
+        nws = ws_bytes(C.byref(Dims(Pc, N, T, O, A, K, self.H, int(self.layernorm))))
         self.update_ws = torch.zeros((nws + 7) // 8, dtype=torch.int64, device=self.dev)
         # sticky OR of every update's exchange-timeout word (workspace word 2P, include/pgm_abi.h): a launch
         # whose spin-wait gave up produced invalid parameters; check_update() turns that into PGMError
@@ -157,17 +171,26 @@ class TaskBatch:
         if self.eval_num > self.HOST_EVAL_MAX:
             raise PGMError(f'host-env mode evaluates at most {self.HOST_EVAL_MAX} episodes per task '
                            f'(eval_num={self.eval_num})')
+        if bool(getattr(he, 'discrete', False)) != self.discrete:
+            raise PGMError(f'host_env.discrete = {getattr(he, "discrete", False)} but {self.env_name} has '
+                           f'{"discrete" if self.discrete else "continuous"} actions')
         E = self.eval_num
-        self._h_act = torch.empty(Pc, N, A, dtype=F32, pin_memory=True)
-        self._d_act = torch.zeros(Pc, N, A, dtype=F32, device=self.dev)
+        if self.discrete:  # one int32 action index per env / evaluation episode
+            self._h_act = torch.empty(Pc, N, dtype=I32, pin_memory=True)
+            self._d_act = torch.zeros(Pc, N, dtype=I32, device=self.dev)
+            A, adt = 1, I32
+        else:
+            self._h_act = torch.empty(Pc, N, A, dtype=F32, pin_memory=True)
+            self._d_act = torch.zeros(Pc, N, A, dtype=F32, device=self.dev)
+            adt = F32
         n = Pc * N * (O + K + 2)
         self._h_tr = torch.zeros(n, dtype=F64, pin_memory=True)
         self._d_tr = torch.zeros(n, dtype=F64, device=self.dev)
         self._tr_ready = None  # the last H2D copy out of _h_tr (the host waits for it before rewriting the buffer)
         self._h_eobs = torch.zeros(Pc * E * O, dtype=F64, pin_memory=True)
         self._d_eobs = torch.zeros(Pc * E * O, dtype=F64, device=self.dev)
-        self._h_eact = torch.empty(Pc * E * A, dtype=F32, pin_memory=True)
-        self._d_eact = torch.zeros(Pc * E * A, dtype=F32, device=self.dev)
+        self._h_eact = torch.empty(Pc * E * A, dtype=adt, pin_memory=True)
+        self._d_eact = torch.zeros(Pc * E * A, dtype=adt, device=self.dev)
 
     def _host_views(self):
         P, N, O, K = self.P, self.N, self.O, self.K
@@ -199,7 +222,17 @@ class TaskBatch:
                                    C.byref(self.c_rb), t, _ptr(do), _ptr(dj), _ptr(dr), _ptr(dd), _ptr(db),
                                    _stream()), 'pgm_env_ingest')
 
+    def _draw_noise(self, seed):
+        """The perf-mode counter stream of `seed` into self.noise: normals, or (discrete) uniforms."""
+        fn, what = ((lib().pgm_uniform_noise, 'pgm_uniform_noise') if self.discrete
+                    else (lib().pgm_normal_noise, 'pgm_normal_noise'))
+        check(fn(self.noise.numel(), C.c_uint64(seed), _ptr(self.noise), _stream()), what)
+
     def _rollout_act(self, t):
+        if self.discrete:
+            check(lib().pgm_rollout_act_cat(C.byref(self.dims), _ptr(self.params), C.byref(self.c_rb), t,
+                                            _ptr(self.noise), _ptr(self._d_act), _stream()), 'pgm_rollout_act_cat')
+            return
         check(lib().pgm_rollout_act(C.byref(self.dims), _ptr(self.params), C.byref(self.c_rb), t, _ptr(self.noise),
                                     _ptr(self._d_act), _stream()), 'pgm_rollout_act')
 
@@ -210,8 +243,7 @@ class TaskBatch:
         import time
         P, T = self.P, self.T
         if noise is None:  # the perf-mode counter stream of `seed`: what the fused rollout draws in-kernel
-            check(lib().pgm_normal_noise(self.noise.numel(), C.c_uint64(seed), _ptr(self.noise), _stream()),
-                  'pgm_normal_noise')
+            self._draw_noise(seed)
         elif noise is not self.noise:
             self.noise.copy_(noise.to(dtype=F32))
         if carry:  # after_update(): slot T -> slot 0 (storage.py:71-75)
@@ -246,18 +278,23 @@ class TaskBatch:
         he = self.host_env
         stream = torch.cuda.current_stream()
         h_obs = self._h_eobs[:P * E * O]
+        if self.discrete:  # int32 action indices [P, E] from pgm_eval_act_cat
+            A = 1
+            eval_act, what, ashape = lib().pgm_eval_act_cat, 'pgm_eval_act_cat', (P, E)
+        else:
+            eval_act, what, ashape = lib().pgm_eval_act, 'pgm_eval_act', (P, E, A)
         h_act = self._h_eact[:P * E * A]
-        obs_np, act_np = h_obs.numpy().reshape(P, E, O), h_act.numpy().reshape(P, E, A)
+        obs_np, act_np = h_obs.numpy().reshape(P, E, O), h_act.numpy().reshape(ashape)
         acc = np.zeros((P, E, K))
         disc = 1.0
         alive = np.ones((P, E), dtype=bool)
         obs = he.eval_reset(E)
-        d = Dims(P, 1, 0, O, A, K, self.H, int(self.layernorm))
+        d = Dims(P, 1, 0, O, self.A, K, self.H, int(self.layernorm))
         while alive.any():
             obs_np[...] = obs
             self._d_eobs[:P * E * O].copy_(h_obs, non_blocking=True)
-            check(lib().pgm_eval_act(C.byref(d), _ptr(self.params), _ptr(mean), _ptr(var), int(self.use_ob_rms),
-                                     _ptr(self._d_eobs), E, _ptr(self._d_eact), _stream()), 'pgm_eval_act')
+            check(eval_act(C.byref(d), _ptr(self.params), _ptr(mean), _ptr(var), int(self.use_ob_rms),
+                           _ptr(self._d_eobs), E, _ptr(self._d_eact), _stream()), what)
             h_act.copy_(self._d_eact[:P * E * A], non_blocking=True)
             stream.synchronize()
             obs, obj, done = he.eval_step(act_np)
@@ -323,8 +360,8 @@ class TaskBatch:
     def _build_structs(self):
         self.dims = Dims(self.P, self.N, self.T, self.O, self.A, self.K, self.H, int(self.layernorm))
         st = self._spec_t
-        self.c_spec = EnvSpec(_ptr(st['d']), _ptr(st['U']), _ptr(st['c']), _ptr(st['V']), _ptr(st['ebase']),
-                              _ptr(st['ecoef']), _ptr(st['act_lo']), _ptr(st['act_hi']),
+        # (a discrete-action env has no SynthMO constants: NULL pointers, and no entry point that reads them is called)
+        self.c_spec = EnvSpec(*(_ptr(st.get(k)) for k in ('d', 'U', 'c', 'V', 'ebase', 'ecoef', 'act_lo', 'act_hi')),
                               self.spec['max_episode_steps'], 0)
         self.c_state = EnvState(_ptr(self.s), _ptr(self.elapsed), _ptr(self.obj_acc), _ptr(self.obj_valid),
                                 _ptr(self.ret), _ptr(self.s0_train))
@@ -376,9 +413,14 @@ class TaskBatch:
         obs = obs.to(device=self.dev, dtype=F32).contiguous()
         d = Dims(P, N, self.T, self.O, self.A, self.K, self.H, int(self.layernorm))
         value = torch.empty(P, N, self.K, dtype=F32, device=self.dev)
-        action = torch.empty(P, N, self.A, dtype=F32, device=self.dev)
         logp = torch.empty(P, N, dtype=F32, device=self.dev)
         nz = None if noise is None else noise.to(device=self.dev, dtype=F32).contiguous()
+        if self.discrete:  # noise: uniforms [N]; the action is the int32 index [P, N]
+            action = torch.empty(P, N, dtype=I32, device=self.dev)
+            check(lib().pgm_act_forward_cat(C.byref(d), _ptr(self.params), _ptr(obs), _ptr(nz), int(deterministic),
+                                            _ptr(value), _ptr(action), _ptr(logp), _stream()), 'pgm_act_forward_cat')
+            return value, action, logp
+        action = torch.empty(P, N, self.A, dtype=F32, device=self.dev)
         check(lib().pgm_act_forward(C.byref(d), _ptr(self.params), _ptr(obs), _ptr(nz), int(deterministic),
                                     _ptr(value), _ptr(action), _ptr(logp), _stream()), 'pgm_act_forward')
         return value, action, logp
@@ -425,7 +467,14 @@ class TaskBatch:
         torch.bitwise_or(self.update_failed, flag, out=self.update_failed)  # stream-ordered, no host sync
 
     def ppo_update_launch(self):
-        """pgm_ppo_update alone (packed rows + the update kernel) on the current stream."""
+        """pgm_ppo_update alone (packed rows + the update kernel) on the current stream; discrete actions:
+        pgm_ppo_update_cat (it gathers from the storage itself: no packed rows)."""
+        if self.discrete:
+            check(lib().pgm_ppo_update_cat(C.byref(self.dims), C.byref(self.hp), _ptr(self.params), _ptr(self.adam_m),
+                                           _ptr(self.adam_v), _ptr(self.adam_step), _ptr(self.lr), _ptr(self.perms),
+                                           C.byref(self.c_rb), _ptr(self.stats), _ptr(self.update_ws), _stream()),
+                  'pgm_ppo_update_cat')
+            return
         check(lib().pgm_ppo_update(C.byref(self.dims), C.byref(self.hp), _ptr(self.params), _ptr(self.adam_m),
                                    _ptr(self.adam_v), _ptr(self.adam_step), _ptr(self.lr), _ptr(self.perms),
                                    C.byref(self.c_rb), _ptr(self.stats), _ptr(self.update_ws),
@@ -433,6 +482,8 @@ class TaskBatch:
 
     def update_variant(self):
         """The update kernel pgm_ppo_update launches for this batch (pgm_ppo_update_variant: the launcher's own rule)."""
+        if self.discrete:  # one kernel, no launch choice
+            return 'ppo_update_cat_kernel (one workgroup per tower)'
         buf = C.create_string_buffer(128)
         check(lib().pgm_ppo_update_variant(C.byref(self.dims), C.byref(self.hp), C.byref(launch_opts()), buf, 128),
               'pgm_ppo_update_variant')
@@ -498,8 +549,7 @@ class TaskBatch:
         if self.host_env is not None:
             overlap_eval = False
         if noise is None:  # perf mode: the counter stream of iteration j, drawn by one wide kernel up front
-            check(lib().pgm_normal_noise(self.noise.numel(), C.c_uint64(j), _ptr(self.noise), _stream()),
-                  'pgm_normal_noise')
+            self._draw_noise(j)
             noise = self.noise
         perm_ready = None
         if perms is None and overlap_eval:  # the permutations (and lr) only feed the update: set beside the rollout

@@ -3,7 +3,7 @@
 //
 // Work split.  Each tower of a task runs on NS workgroups (2 NS per task, all on one XCD under round-robin dispatch);
 // workgroup hs takes its share of every minibatch's 16-row tiles: R = ceil(mb / (16 NS)) (NS = 6: 3 / 3 / 3 / 3 / 2 / 2
-// on a 256-row minibatch, a missing tile a zero-gradient dummy).  Inside
+// on a 256-row minibatch; a part with a tile fewer runs the tile passes without it).  Inside
 // a workgroup the FOUR WAVES SPLIT THE 64 HIDDEN FEATURES (wave w: features 16w .. 16w + 15) instead of the rows, on
 // the v_mfma_f32_16x16x4_f32 layout
 //     C/D: lane l, register r <-> (row 4(l >> 4) + r, column l & 15); A: lane l holds A[l & 15][l >> 4];
@@ -166,7 +166,8 @@ struct FsSmem {
     alignas(16) float HP[NHP][SB][DQS];                        // R < 4: the waves' partial head outputs (after B3:
                                                                // the waves' compact head-block staging, 128 floats each)
     float aiv[A];                                              // actor 1 / std^2
-    float red[192];  // [0, 64) head-bias partials / poll results, [64, 128) logstd partials / norms, 128+ loss sums
+    float red[192];  // [0, 64) head-bias partials / poll results, [64, 128) logstd partials / norms, 128+ loss sums,
+                     // 136 / 137 the step's Adam scalars (fs)
 };
 // one workgroup per CU: padded past 80 KiB (the placement the launcher's grid assumes); dual (two per CU, 16 NS ceil(P/8)
 // > CUs): the struct itself, which must then fit 80 KiB
@@ -177,10 +178,26 @@ constexpr size_t fs_smem_bytes(bool dual) {
 
 // (Measured and dropped: the parameter hop without a flag -- owners storing every new value as an 8-B {value, tag}
 // granule, readers re-loading a block until all its tags are this step's: P = 5 3.45 vs 2.93 ms, P = 20 5.06 vs 4.38 ms.)
-template <int O, int A, int K, int NS, int R>
-// R = 3: held to 256 registers, so that two workgroups share a CU (fs_choose_ns dual; R = 2 fits by itself)
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(R == 3 ? 2 : 1))) void ppo_update_fs_kernel(MArgs a) {
+//
+// The whole update of one workgroup is a device function that can be built for one tower: MT = 0 critic, 1 actor,
+// selected once by the kernel from blockIdx; MT = -1 takes the tower m at run time.  With MT fixed the step loop of a
+// critic workgroup carries none of the actor's loss code, operands and lane masks (NQ, the packed surrogate, logstd,
+// 1 / std^2, entropy_coef) and the reverse -- uniform values that otherwise sit in SGPRs for the whole launch and
+// overflow into VGPR lanes.  Used where it measured as a gain: 6 parts of 3 tiles, two workgroups per CU (Walker
+// P = 40 -0.07 ms per launch); with one workgroup per CU (Walker P = 5, +0.08 ms) and at R = 2 it did not pay, and those
+// instances keep the run-time tower.
+//
+// RT = the 16-row tiles this part really has (6 parts: R = 3 dealt 3 / 3 / 3 / 3 / 2 / 2 on 256 rows; else RT = R),
+// also fixed per workgroup: a part with a tile fewer runs the tile passes without it.  The LDS layout and the staging
+// stay those of R tiles.  What the missing tile contributed before were exact zeros -- its dO and loss terms were
+// zeroed, so its head-weight, dZ2, dW2, dZ1, dW1 and bias terms were 0 x finite products added to accumulators that
+// are never -0 -- so every sum keeps its bits.
+template <int O, int A, int K, int NS, int R, int MT, int RT>
+__device__ __forceinline__ void fs_update_tower(const MArgs& a, const int p, const int hs, const int m_) {
     static_assert(O <= 32 && (R == 1 || R == 2 || R == 3 || R == 4 || R == 8), "fs tiles");
+    static_assert(MT >= -1 && MT <= 1, "tower");
+    static_assert(RT == R || (NS == 6 && R == 3 && RT == 2), "tiles of a part");
+    const int m = MT < 0 ? m_ : MT;
     using Sm = FsSmem<O, A, K, R>;
     extern __shared__ __attribute__((aligned(16))) char smem_raw[];
     auto& S = *reinterpret_cast<Sm*>(smem_raw);
@@ -201,20 +218,13 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(R == 3 ? 2 
     constexpr int oW2 = O * H, oWh = oW2 + H * SCR, oB1 = oWh + Q * H, oB2 = oB1 + H, oBh = oB2 + H, oLs = oBh + Q;
     const int t = threadIdx.x, l = t & 63, g = l >> 4, c = l & 15;
     const int w = __builtin_amdgcn_readfirstlane(t >> 6);
-    // block map: groups of 16 NS blocks for 8 tasks; block r holds part (r >> 4) % NS of tower (r >> 3) & 1 of task
-    // 8 G + (r & 7), so every workgroup of a task shares blocks b, b + 8, ... (one XCD: speed only)
-    const int bx = (int)blockIdx.x;
-    const int j16 = (bx >> 3) % (2 * NS);
-    const int p = 8 * (bx / (16 * NS)) + (bx & 7);
-    const int hs = j16 >> 1, m = j16 & 1;
-    if (p >= a.P) return;
     const int NQ = m == 0 ? K : A;
     const int N = a.N, T = a.T, B = T * N;
     const int E = a.hp.ppo_epoch, M = a.hp.num_mini_batch;
     const int mb = B / M, nb = B / mb;
     // this part's rows of every minibatch: the mb / 16 row tiles dealt over the NS parts, the first (mb / 16) % NS parts
-    // one more (NS = 6 on a 256-row minibatch: 3 / 3 / 3 / 3 / 2 / 2); tiles past the part's own count are dummies
-    // (their rows repeat its last one) whose loss gradients and loss terms are zeroed, so they add exact zeros
+    // one more (NS = 6 on a 256-row minibatch: 3 / 3 / 3 / 3 / 2 / 2); the staging still fills R tiles (rows past the
+    // part's own repeat its last one), the tile passes run the RT = rown / 16 real ones
     const int ntl = mb >> 4, tb0 = ntl / NS, tex = ntl - tb0 * NS;
     const int rown = 16 * (tb0 + (hs < tex ? 1 : 0));
     const int r0 = 16 * (hs * tb0 + min(hs, tex));
@@ -228,6 +238,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(R == 3 ? 2 
     const int fsbytes = (int)((size_t)a.P * 2 * NS * 2 * (ISB + PSB));
     const __amdgpu_buffer_rsrc_t xr = __builtin_amdgcn_make_buffer_rsrc(a.fsp, 0, fsbytes, 0x00020000);
     constexpr int SC1 = 16;
+    // payload offsets: the scalar part (slot of part h, parity par) goes into the buffer instruction's soffset, the
+    // per-thread part (block, lane) is a VGPR fixed for the launch -- no per-access address arithmetic on the VALU
     auto islot = [&](int h, int par) { return ((((p * 2 + m) * NS + h) * 2 + par)) * ISB; };
     auto pslot = [&](int h, int par) { return a.P * 2 * NS * 2 * ISB + ((((p * 2 + m) * NS + h) * 2 + par)) * PSB; };
     auto gran = [&](int kind, int mm, int h, int par) { return a.ws + fs_gran(a.P, NS, kind, p, mm, h, par); };
@@ -329,10 +341,28 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(R == 3 ? 2 
             }
         }
     };
+    int pvo[BPW];  // (own part's blocks too: straight-line loads)
+#pragma unroll
+    for (int k = 0; k < BPW; ++k) {
+        const int b = BPW * w + k, h = b % NS, jj = b / NS;
+        pvo[k] = pslot(h, 0) + (jj * 64 + l) * 16;
+        asm volatile("" : "+v"(pvo[k]));
+    }
     auto pload = [&](int k, int par_) {
-        const int b = BPW * w + k, h = b % NS, jj = b / NS;  // (own part's blocks too: straight-line loads)
-        pv[k] = __builtin_amdgcn_raw_buffer_load_b128(xr, pslot(h, par_) + (jj * 64 + l) * 16, 0, SC1);
+        pv[k] = __builtin_amdgcn_raw_buffer_load_b128(xr, pvo[k], par_ * PSB, SC1);
     };
+    // this wave's gradient blocks in the part's image slot (block k: + 1 KiB), its owned blocks in every part's image
+    // slot (reduce-scatter; past NB: beyond the buffer's range, which returns zeros) and in its parameter slot
+    int pubo = (w * BPW * 64 + l) * 16;
+    asm volatile("" : "+v"(pubo));
+    int rso[OWV], pso[OWV];
+#pragma unroll
+    for (int i = 0; i < OWV; ++i) {
+        const int b = hs + NS * (w + 4 * i);
+        rso[i] = b < NB ? (b * 64 + l) * 16 : 0x7ffffff0;
+        pso[i] = ((w + 4 * i) * 64 + l) * 16;
+        asm volatile("" : "+v"(rso[i]), "+v"(pso[i]));
+    }
     for (int gp = 0; gp < npass; ++gp) {
         const int cur = gp & 1, par = gp & 1;
         const unsigned tag = (unsigned)(gp + 1);
@@ -348,7 +378,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(R == 3 ? 2 
         // ---- layer 1: Z1[s][fb + c] over the inputs (A = X rows, B = W1t, shared by the tiles)
         f32x4 z[R][NC], H1[R];
 #pragma unroll
-        for (int ti = 0; ti < R; ++ti)
+        for (int ti = 0; ti < RT; ++ti)
 #pragma unroll
             for (int q = 0; q < NC; ++q) z[ti][q] = f32x4{0.f, 0.f, 0.f, 0.f};
         // (compact: inputs 16.. -- at most 4, one mostly-padding k-step -- on the VALU, added below)
@@ -359,7 +389,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(R == 3 ? 2 
             const bool kv = k < O;
             const float bw = kv ? Wt.W1t[kv ? k : 0][fb + c] : 0.f;
 #pragma unroll
-            for (int ti = 0; ti < R; ++ti) {
+            for (int ti = 0; ti < RT; ++ti) {
                 const float av = kv ? rt(ti)[c * RSL + (kv ? k : 0)] : 0.f;
                 z[ti][ks % NC] = mfma16(av, bw, z[ti][ks % NC]);
             }
@@ -369,7 +399,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(R == 3 ? 2 
 #pragma unroll
             for (int j = 0; j < NT1; ++j) w16[j] = Wt.W1t[16 + j][fb + c];
 #pragma unroll
-            for (int ti = 0; ti < R; ++ti)
+            for (int ti = 0; ti < RT; ++ti)
 #pragma unroll
                 for (int r = 0; r < 4; ++r) {
                     const float* xr16 = rt(ti) + (4 * g + r) * RSL + 16;
@@ -380,7 +410,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(R == 3 ? 2 
         {
             const float bias = Wt.b1[fb + c];
 #pragma unroll
-            for (int ti = 0; ti < R; ++ti) {
+            for (int ti = 0; ti < RT; ++ti) {
                 f32x4 zz = z[ti][0];
                 if constexpr (NC == 2) zz += z[ti][1];
                 tanh_bias_pk<4>(zz, bias, H1[ti]);
@@ -402,7 +432,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(R == 3 ? 2 
         // ---- layer 2: Z2[s][fb + c] = H1[s][:] . W2t[:][fb + c]
         f32x4 H2[R];
 #pragma unroll
-        for (int ti = 0; ti < R; ++ti)
+        for (int ti = 0; ti < RT; ++ti)
 #pragma unroll
             for (int q = 0; q < NC; ++q) z[ti][q] = f32x4{0.f, 0.f, 0.f, 0.f};
         // k-step (j, i) contracts input k = 16 j + 4 g + i in lane group g: four consecutive inputs per lane and j, so
@@ -413,7 +443,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(R == 3 ? 2 
 #pragma unroll
             for (int i = 0; i < 4; ++i) bw[i] = Wt.W2t[16 * j + 4 * g + i][fb + c];
 #pragma unroll
-            for (int ti = 0; ti < R; ++ti) {
+            for (int ti = 0; ti < RT; ++ti) {
                 const float4 a4 = *reinterpret_cast<const float4*>(&S.H1s[16 * ti + c][16 * j + 4 * g]);
                 const float av[4] = {a4.x, a4.y, a4.z, a4.w};
 #pragma unroll
@@ -423,7 +453,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(R == 3 ? 2 
         {
             const float bias = Wt.b2[fb + c];
 #pragma unroll
-            for (int ti = 0; ti < R; ++ti) {
+            for (int ti = 0; ti < RT; ++ti) {
                 f32x4 zz = z[ti][0];
                 if constexpr (NC == 2) zz += z[ti][1];
                 tanh_bias_pk<4>(zz, bias, H2[ti]);
@@ -513,7 +543,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(R == 3 ? 2 
             const float4 b4 = qv ? *reinterpret_cast<const float4*>(&Wt.Wh[qv ? c : 0][fb + 4 * g]) : make_float4(0.f, 0.f, 0.f, 0.f);
             const float bv[4] = {b4.x, b4.y, b4.z, b4.w};
 #pragma unroll
-            for (int ti = 0; ti < R; ++ti) {
+            for (int ti = 0; ti < RT; ++ti) {
                 f32x4 ho = f32x4{0.f, 0.f, 0.f, 0.f};
                 const float4 a4 = *reinterpret_cast<const float4*>(&S.H2s[16 * ti + c][fb + 4 * g]);
                 const float av[4] = {a4.x, a4.y, a4.z, a4.w};
@@ -535,8 +565,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(R == 3 ? 2 
                 const float aivp = S.aiv[avp ? cc : 0], lsp = avp ? Wt.logstd[avp ? cc : 0] : 0.f;
                 const float bhp = avp ? Wt.bh[avp ? cc : 0] : 0.f;
 #pragma unroll
-                for (int p2 = 0; p2 < R; p2 += 2) {
-                    const bool tin = p2 + hf < R;  // (R odd: the last pass's upper half recomputes tile p2, zeroed)
+                for (int p2 = 0; p2 < RT; p2 += 2) {
+                    const bool tin = p2 + hf < RT;  // (RT odd: the last pass's upper half recomputes tile p2, zeroed)
                     const int ti = tin ? p2 + hf : p2, row = 16 * ti + 4 * g + w;
                     const bool tv = tin && 16 * ti < rown;
                     const float out = ((S.HP[0][row][cc] + S.HP[1][row][cc]) + S.HP[2][row][cc]) + S.HP[3][row][cc] + bhp;
@@ -563,7 +593,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(R == 3 ? 2 
                 gls += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(gls), 0x128, 0xf, 0xf, true));
             } else {
 #pragma unroll
-                for (int ti = 0; ti < R; ++ti) {
+                for (int ti = 0; ti < RT; ++ti) {
                     const int s = 4 * g + w, row = 16 * ti + s;
                     const int cq = c < DQ ? c : 0;
                     const float out = c < DQ ? ((S.HP[0][row][cq] + S.HP[1][row][cq]) + S.HP[2][row][cq]) + S.HP[3][row][cq] : 0.f;
@@ -598,7 +628,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(R == 3 ? 2 
         float (*Zt)[SF] = Sm::ZA ? S.H2s : S.Zs;
         f32x4 dZ2[R];
 #pragma unroll
-        for (int ti = 0; ti < R; ++ti) {
+        for (int ti = 0; ti < RT; ++ti) {
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
                 const float bo = qv ? dtl[(16 * ti + 4 * g + r) * DQS + (qv ? c : 0)] : 0.f;
@@ -638,7 +668,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(R == 3 ? 2 
         // this wave's dW2 / head-weight blocks are final: out now (write-through under the dH1 / dW1 pass)
         auto pub = [&](int k, const f32x4& v) {
             const u32x4 u = {__float_as_uint(v[0]), __float_as_uint(v[1]), __float_as_uint(v[2]), __float_as_uint(v[3])};
-            __builtin_amdgcn_raw_buffer_store_b128(u, xr, islot(hs, par) + ((w * BPW + k) * 64 + l) * 16, 0, SC1);
+            __builtin_amdgcn_raw_buffer_store_b128(u, xr, pubo + k * 1024, islot(hs, par), SC1);
         };
 #pragma unroll
         for (int ib = 0; ib < 4; ++ib) pub(K1M + ib, gW2[ib]);
@@ -647,7 +677,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(R == 3 ? 2 
         lds_sync_m();  // B3: dZ2 of every feature block
         // ---- dH1 = dZ2 W2 for this wave's input block, dZ1, dW1^T[k][fb + c] += X^T dZ1
 #pragma unroll
-        for (int ti = 0; ti < R; ++ti)
+        for (int ti = 0; ti < RT; ++ti)
 #pragma unroll
             for (int q = 0; q < NC; ++q) z[ti][q] = f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
@@ -656,7 +686,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(R == 3 ? 2 
 #pragma unroll
             for (int i = 0; i < 4; ++i) bw[i] = Wt.W2t[fb + c][16 * j + 4 * g + i];
 #pragma unroll
-            for (int ti = 0; ti < R; ++ti) {
+            for (int ti = 0; ti < RT; ++ti) {
                 const float4 a4 = *reinterpret_cast<const float4*>(&Zt[16 * ti + c][16 * j + 4 * g]);
                 const float av[4] = {a4.x, a4.y, a4.z, a4.w};
 #pragma unroll
@@ -664,7 +694,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(R == 3 ? 2 
             }
         }
 #pragma unroll
-        for (int ti = 0; ti < R; ++ti) {
+        for (int ti = 0; ti < RT; ++ti) {
             f32x4 zz = z[ti][0], dZ1;
             if constexpr (NC == 2) zz += z[ti][1];
             dtanh_pk<4>(zz, H1[ti], dZ1);
@@ -770,11 +800,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(R == 3 ? 2 
             u32x4 pl[OWV][NS];
 #pragma unroll
             for (int i = 0; i < OWV; ++i) {
-                const int b = hs + NS * (w + 4 * i);
 #pragma unroll
                 for (int h = 0; h < NS; ++h)
-                    pl[i][h] = __builtin_amdgcn_raw_buffer_load_b128(
-                        xr, b < NB ? islot(h, par) + (b * 64 + l) * 16 : 0x7ffffff0, 0, SC1);
+                    pl[i][h] = __builtin_amdgcn_raw_buffer_load_b128(xr, rso[i], islot(h, par), SC1);
             }
 #pragma unroll
             for (int i = 0; i < OWV; ++i) {
@@ -797,17 +825,23 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(R == 3 ? 2 
         if (t == 0)
             __hip_atomic_store(gran(1, m, hs, par), ((unsigned long long)tag << 32) | __float_as_uint(sq_wg),
                                __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        // this step's Adam scalars (fp64 bias corrections) while the granules travel
-        const double b1n = b1p * (double)b1c, b2n = b2p * (double)b2c;
-        float step_size = (float)(lr / (1.0 - b1n));
-        float inv_bc2s = 1.f / (float)sqrt(1.0 - b2n);
-        asm volatile("" : "+v"(step_size), "+v"(inv_bc2s));
+        // this step's Adam scalars (fp64 bias corrections) while the granules travel: one lane of a wave that does not
+        // poll evaluates them (the expressions every lane used to evaluate, so the same bits) and hands the two floats
+        // over in LDS behind the barrier after the poll
+        if (t == 64) {
+            b1p = b1p * (double)b1c;
+            b2p = b2p * (double)b2c;
+            S.red[136] = (float)(lr / (1.0 - b1p));
+            S.red[137] = 1.f / (float)sqrt(1.0 - b2p);
+        }
         if (w == 0 && l < 2 * NS) {
             dbg_delay(a.dbg, gp, 2);
             const int mm = l / NS, hh = l - mm * NS;
             S.red[64 + l] = mm == m && hh == hs ? sq_wg : __uint_as_float((unsigned)spin(gran(1, mm, hh, par), 1));
         }
         lds_sync_m();
+        float step_size = S.red[136], inv_bc2s = S.red[137];
+        asm volatile("" : "+v"(step_size), "+v"(inv_bc2s));
         float total = 0.f;
 #pragma unroll
         for (int i = 0; i < 2 * NS; ++i) total += S.red[64 + i];
@@ -820,8 +854,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(R == 3 ? 2 
             for (int q = 0; q < A; ++q) ent += 0.5f + LOG_SQRT_2PI + Wt.logstd[q];
             st_e += ent;
         }
-        b1p = b1n;
-        b2p = b2n;
         PGM_STAMP(8);
         dbg_delay(a.dbg, gp, 3);
         auto adam = [&](float gg, float& mm_, float& vv_, float& pp_) {
@@ -850,10 +882,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(R == 3 ? 2 
             }
             // the part's owned block w + 4 i (slot position always valid: blocks past NB publish unused values, so every
             // wave issues the same number of stores)
-            const int jj = w + 4 * i;
             const u32x4 u = {__float_as_uint(op[i][0]), __float_as_uint(op[i][1]), __float_as_uint(op[i][2]),
                              __float_as_uint(op[i][3])};
-            __builtin_amdgcn_raw_buffer_store_b128(u, xr, pslot(hs, par) + (jj * 64 + l) * 16, 0, SC1);
+            __builtin_amdgcn_raw_buffer_store_b128(u, xr, pso[i], pslot(hs, par), SC1);
         }
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // + the row DMA issued during the image poll
         lds_sync_m();
@@ -896,6 +927,31 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(R == 3 ? 2 
             a.stats[p * 3 + 1] = st_a / n;
             a.stats[p * 3 + 2] = st_e / n;
         }
+    }
+}
+
+template <int O, int A, int K, int NS, int R>
+// R = 3: held to 256 registers, so that two workgroups share a CU (fs_choose_ns dual; R = 2 fits by itself)
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(R == 3 ? 2 : 1))) void ppo_update_fs_kernel(MArgs a) {
+    // block map: groups of 16 NS blocks for 8 tasks; block r holds part (r >> 4) % NS of tower (r >> 3) & 1 of task
+    // 8 G + (r & 7), so every workgroup of a task shares blocks b, b + 8, ... (one XCD: speed only)
+    const int bx = (int)blockIdx.x;
+    const int j16 = (bx >> 3) % (2 * NS);
+    const int p = 8 * (bx / (16 * NS)) + (bx & 7);
+    const int hs = j16 >> 1, m = j16 & 1;
+    if (p >= a.P) return;
+    if constexpr (NS == 6 && R == 3) {
+        // the part's own tiles (as fs_update_tower deals them): 3 or 2
+        const int mb = a.T * a.N / a.hp.num_mini_batch, ntl = mb >> 4, tb0 = ntl / NS;
+        if (tb0 + (hs < ntl - tb0 * NS ? 1 : 0) < R) {
+            if (m == 0) fs_update_tower<O, A, K, NS, R, 0, 2>(a, p, hs, 0);
+            else fs_update_tower<O, A, K, NS, R, 1, 2>(a, p, hs, 1);
+        } else {
+            if (m == 0) fs_update_tower<O, A, K, NS, R, 0, R>(a, p, hs, 0);
+            else fs_update_tower<O, A, K, NS, R, 1, R>(a, p, hs, 1);
+        }
+    } else {
+        fs_update_tower<O, A, K, NS, R, -1, R>(a, p, hs, m);
     }
 }
 

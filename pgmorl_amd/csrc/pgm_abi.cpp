@@ -60,6 +60,24 @@ int check_coresident(const void* kern, int block, size_t smem, int grid, const c
     return PGM_OK;
 }
 
+int prepare_update_launch(const void* kern, int block, size_t smem, int resident, void* ws, size_t zero_bytes,
+                          hipStream_t stream, const char* what) {
+    hipError_t e = hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
+    if (e != hipSuccess) return hip_fail(e, what);
+    if (resident > 0) {
+        if (int rc = check_coresident(kern, block, smem, resident, what)) return rc;
+    }
+    if (!ws_take_zeroed(ws, zero_bytes)) {
+        e = hipMemsetAsync(ws, 0, zero_bytes, stream);
+        if (e != hipSuccess) {
+            char reset[96];
+            snprintf(reset, sizeof(reset), "%s (workspace reset)", what);
+            return hip_fail(e, reset);
+        }
+    }
+    return PGM_OK;
+}
+
 DbgDelay dbg_delay_hook() {
     DbgDelay d{0, 0, 0, 0u};
 #ifdef PGM_TEST_HOOKS

@@ -90,6 +90,13 @@ int device_cu_count();  // CUs of the current device (cached)
 // block size and LDS must admit grid <= blocks-per-CU x CUs.  PGM_E_UNSUPPORTED (with the numbers) otherwise.
 int check_coresident(const void* kern, int block, size_t smem, int grid, const char* what);
 
+// The host sequence ahead of an update kernel's launch, in this order: opt the kernel into smem bytes of dynamic LDS;
+// check_coresident for `resident` workgroups (0: the workgroups do not wait on each other, no check); hand over
+// zero_bytes zeroed workspace bytes -- the pgm_ppo_update_reset mark if it covers them, a memset on the stream
+// otherwise ("<what> (workspace reset)" when that fails).
+int prepare_update_launch(const void* kern, int block, size_t smem, int resident, void* ws, size_t zero_bytes,
+                          hipStream_t stream, const char* what);
+
 // Launch options with NULL = automatic, validated (pgm_abi.h pgm_launch_opts).
 int read_opts(const pgm_launch_opts* o, pgm_launch_opts* out, const char* what);
 // Row-split cap of opts->update_split: 4 (four per tower), 2, 1 (one per tower), 0 (one per task); 4 when automatic.

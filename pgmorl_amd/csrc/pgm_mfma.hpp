@@ -3,6 +3,7 @@
 //     lane l, register r  <->  (sample rowof(r, l>>5), feature l & 31),  rowof(r,h) = (r&3)+8(r>>2)+4h.
 #pragma once
 #include "pgm_common.hpp"
+#include "pgm_ppo_terms.hpp"
 
 namespace pgm {
 
@@ -54,10 +55,6 @@ __device__ __forceinline__ float group4_sum(float v) {
     v = half_sum(v);                   // l ^ 32 (v_permlane32_swap)
     return v + __shfl_xor(v, 16, 64);  // l ^ 16
 }
-
-// torch.min(a,b) / torch.max(a,b) backward weights for the first argument (ties split the gradient in half)
-__device__ __forceinline__ float wmin2(float a, float b) { return a < b ? 1.f : (a == b ? 0.5f : 0.f); }
-__device__ __forceinline__ float wmax2(float a, float b) { return a > b ? 1.f : (a == b ? 0.5f : 0.f); }
 
 typedef float f2v __attribute__((ext_vector_type(2)));
 

@@ -478,6 +478,7 @@ __device__ __forceinline__ void fs_update_tower(const MArgs& a, const int p, con
                 const bool ok = c < K && tv;
                 const float Vold = rr[s * RSL + O + A + 2 + (c < K ? c : 0)];
                 const float Rt = rr[s * RSL + O + A + 2 + K + (c < K ? c : 0)];
+                // restates value_loss_term (pgm_ppo_terms.hpp): moving it changes this file's register allocation
                 float gv, ls;
                 if (a.hp.use_clipped_value_loss) {
                     const float dv = out - Vold;
@@ -500,6 +501,7 @@ __device__ __forceinline__ void fs_update_tower(const MArgs& a, const int p, con
             const float lpe = av_ ? -0.5f * diff * diff * aiv - ls_c - LOG_SQRT_2PI : 0.f;
             const float lp = row_sum16(lpe);
             const float ratio = expf(lp - rr[s * RSL + O + A]);
+            // restates surrogate_term (pgm_ppo_terms.hpp): moving it changes this file's register allocation
             const float ad = rr[s * RSL + O + A + 1];
             const float s1 = ratio * ad;
             const float s2 = fminf(fmaxf(ratio, 1.f - clip), 1.f + clip) * ad;
@@ -576,6 +578,7 @@ __device__ __forceinline__ void fs_update_tower(const MArgs& a, const int p, con
                     const float lpe = avp ? -0.5f * diff * diff * aivp - lsp - LOG_SQRT_2PI : 0.f;
                     const float lp = row_sum8(lpe);
                     const float ratio = expf(lp - q[A]);
+                    // restates surrogate_term (pgm_ppo_terms.hpp): moving it changes this file's register allocation
                     const float ad = q[A + 1];
                     const float s1 = ratio * ad;
                     const float s2 = fminf(fmaxf(ratio, 1.f - clip), 1.f + clip) * ad;
@@ -767,15 +770,7 @@ __device__ __forceinline__ void fs_update_tower(const MArgs& a, const int p, con
         // spin on a tagged granule (bounded; a timeout marks the launch failed and every later poll skips)
         auto spin = [&](const unsigned long long* gr, int site) -> unsigned long long {
             if (__hip_atomic_load(fail_word, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) return 0ull;
-            for (unsigned spins = 0;; ++spins) {
-                const unsigned long long x = __hip_atomic_load(gr, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                if ((unsigned)(x >> 32) == tag) return x;
-                if (spins > (1u << 26)) {
-                    __hip_atomic_store(fail_word, fail_code(site, tag), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    return 0ull;
-                }
-                __builtin_amdgcn_s_sleep(1);
-            }
+            return poll_tagged(gr, tag, fail_word, fail_code(site, tag));
         };
         if (w == 0) {
             if (l < NS) {  // lane h polls part h's image flag (the NS - 1 polls run concurrently)
@@ -828,7 +823,7 @@ __device__ __forceinline__ void fs_update_tower(const MArgs& a, const int p, con
         // this step's Adam scalars (fp64 bias corrections) while the granules travel: one lane of a wave that does not
         // poll evaluates them (the expressions every lane used to evaluate, so the same bits) and hands the two floats
         // over in LDS behind the barrier after the poll
-        if (t == 64) {
+        if (t == 64) {  // restates AdamScalars::advance (pgm_ppo_terms.hpp): moving it changes this file's register allocation
             b1p = b1p * (double)b1c;
             b2p = b2p * (double)b2c;
             S.red[136] = (float)(lr / (1.0 - b1p));
@@ -857,11 +852,7 @@ __device__ __forceinline__ void fs_update_tower(const MArgs& a, const int p, con
         PGM_STAMP(8);
         dbg_delay(a.dbg, gp, 3);
         auto adam = [&](float gg, float& mm_, float& vv_, float& pp_) {
-            const float gc = gg * coef;
-            mm_ = mm_ + (1.f - b1c) * (gc - mm_);
-            vv_ = vv_ * b2c + (1.f - b2c) * (gc * gc);
-            const float den = __builtin_amdgcn_sqrtf(vv_) * inv_bc2s + eps;
-            pp_ -= step_size * mm_ * __builtin_amdgcn_rcpf(den);
+            adam_step(gg, coef, mm_, vv_, pp_, b1c, b2c, step_size, inv_bc2s, eps);
         };
         // ---- 4. Adam on the owned blocks (registers), publish them, write them into this part's image
 #pragma unroll

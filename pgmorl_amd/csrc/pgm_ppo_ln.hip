@@ -2,16 +2,16 @@
 // (v_mfma_f32_32x32x2_f32, exact fp32): ppo_update_ln_kernel.
 //
 // Each tower layer is Linear(bias=False) -> LayerNorm(64, elementwise_affine) -> tanh (a2c_ppo_acktr/model.py:201-256
-// with layernorm=True).  Work split of the row-split kernel's one-workgroup-per-tower mode (pgm_ppo_mfma.hip MODE 1):
-// two 256-thread workgroups per task, critic and actor, both on one XCD; the tower's parameters AND Adam moments stay
-// in LDS for the whole launch (one HBM read at the start, one write at the end); the only coupling inside a minibatch
-// step is the squared gradient norm, exchanged as the tagged 8-byte norm granule of pgm_common.hpp (ppo_norm_granule,
-// double-buffered by step parity, the same spin limit and timeout word 2P).
+// with layernorm=True).  One 256-thread workgroup per tower, two per task, parameters and Adam moments LDS-resident,
+// the squared gradient norm the only coupling inside a step: the work split, the tile layout (samples on accumulator
+// registers, features on lanes) and every phase but the ones below are the shared tower functions of
+// pgm_ppo_tower.hpp (which ppo_update_cat_kernel is built from as well); the loss terms, clip_grad_norm_ and Adam are
+// pgm_ppo_terms.hpp's (a2c_ppo_acktr/algo/ppo.py:58-115).  This file holds what is LayerNorm's own: the image with
+// gamma / beta slots, the normalisation tiles handed to the shared tile functions as the activation and its backward,
+// the Gaussian actor loss, the logstd slot and the 1 / std^2 refresh after Adam.
 //
-// Tiles of 32 samples per wave; samples are the accumulator ROWS (registers), features the COLUMNS (lanes):
-//     lane l, register r  <->  (sample rowof(r, l>>5), feature l & 31 of column tile 0 / 1).
-// A sample's 64 pre-activations therefore sit in ONE register index of the two column tiles over the 32 lanes of a
-// half-wave: the LayerNorm row statistics (mean, variance of the mean-subtracted values; in the backward pass
+// In that layout a sample's 64 pre-activations sit in ONE register index of the two column tiles over the 32 lanes of
+// a half-wave: the LayerNorm row statistics (mean, variance of the mean-subtracted values; in the backward pass
 // mean(g) and mean(g xhat)) are sums over the two tiles and the 32 lanes of the half -- one v_permlane16_swap and
 // four DPP row rotations each, no LDS and no cross-wave traffic.  The gamma / beta gradients sum over samples, i.e.
 // over registers, per lane, like the bias gradients of the plain kernels.
@@ -24,12 +24,11 @@
 // reaches dgamma / dbeta, and 1e-5 keeps r finite at z = 0.
 //
 // The minibatch rows are gathered straight from the rollout storage through the permutation (no packed table).
-// Losses, clip_grad_norm_ and Adam are those of the plain kernels (a2c_ppo_acktr/algo/ppo.py:58-115).
 #include <stdio.h>
 #include <stdlib.h>
 
 #include "pgm_dispatch.hpp"
-#include "pgm_ppo_shared.hpp"
+#include "pgm_ppo_tower.hpp"
 
 PGM_STAMP_UNIT(ln)
 
@@ -44,9 +43,6 @@ struct LnImg {
     float Wh[Q][H];
     float g1[H], be1[H], g2[H], be2[H], bh[Q], logstd[A];
 };
-template <int O, int A, int K>
-constexpr int ln_img_floats() { return (int)(sizeof(LnImg<O, A, K>) / sizeof(float)); }
-
 // image slot -> flat parameter index (pgm_param_layout_ln order), -1 for padding / unused slots
 template <int O, int A, int K>
 __device__ __forceinline__ int ln_img_to_flat(int i, int m, const LayoutLN& L) {
@@ -72,42 +68,14 @@ __device__ __forceinline__ int ln_img_to_flat(int i, int m, const LayoutLN& L) {
     return -1;
 }
 
-struct LnArgs {
-    int P, N, T;
-    LayoutLN L;
-    pgm_ppo_hparams hp;
-    float *params, *m, *v;
-    int32_t* step;
-    const float* lr;
-    const int32_t* perms;
-    const float *obs, *actions, *logp, *values, *returns, *adv;
-    float* stats;
-    unsigned long long* ws;  // tagged norm granules + timeout word (2P), zeroed before the launch
-    DbgDelay dbg;            // test-only exchange delay (PGM_TEST_DELAY; cycles 0 = off)
-};
+using LnArgs = TowerArgs<LayoutLN>;
 
+// obs | action | old logp | adv | old value | return; the actor's per-sample logstd terms and 1 / std^2 on top
 template <int O, int A, int K>
-struct LnSmem {
-    static constexpr int Q = qmax<A, K>();
-    static constexpr int IMG = ln_img_floats<O, A, K>();
-    static constexpr int NC = O + A + 2 + 2 * K;  // obs | action | old logp | adv | old value | return
-    static constexpr int RW = NC | 1;             // odd row stride: conflict-free per-sample column reads
-    LnImg<O, A, K> Pm;                            // parameters
-    float MV[2 * IMG];                            // Adam exp_avg | exp_avg_sq images
-    float rows[4][TS][RW];                        // per-wave gathered samples of the current tile
-    float dout[4][TS][Q];                         // per-wave dL/d(head output) of the current tile
-    float dls[4][TS][Q];                          // per-wave per-sample dL/d(logstd) of the current tile (actor)
-    float aiv[A];                                 // actor 1 / std^2 = exp(-2 logstd), refreshed by Adam
-    float red[16];
-    union Big {                                   // transpose tiles during the tiles, the gradient image after
-        float scr[4][TS][SCR];
-        float G[IMG];
-    } big;
+struct LnSmem : TowerSmem<LnImg<O, A, K>, O + A + 2 + 2 * K, qmax<A, K>()> {
+    float dls[4][TS][qmax<A, K>()];  // per-wave per-sample dL/d(logstd) of the current tile (actor)
+    float aiv[A];                    // actor 1 / std^2 = exp(-2 logstd), refreshed by Adam
 };
-
-// blocks of the launch: groups of 16 for 8 tasks, block r of a group = tower (r >> 3) & 1 of task 8 g + (r & 7), so
-// a task's two workgroups share an XCD under round-robin dispatch (padding blocks of a partial group exit at once)
-inline int ln_grid(int P) { return 16 * ((P + 7) / 8); }
 
 // sum over the 32 lanes of each half-wave, result in all of them: fold the two 16-lane rows of the half
 // (v_permlane16_swap), then four DPP rotations inside the row
@@ -118,9 +86,9 @@ __device__ __forceinline__ float rsqrt_nr(float x) {
     return r * fmaf(-0.5f * x * r, r, 1.5f);
 }
 
-// LayerNorm + affine + tanh of one tile in C layout: z (two column tiles) -> xhat (in place), rstd per register, h
-__device__ __forceinline__ void ln_forward_tile(f32x16 (&z)[2], float (&rs)[16], f32x16 (&hout)[2], const float* g,
-                                                const float* be, int c) {
+// LayerNorm + affine + tanh of one tile in C layout: z (two column tiles) -> xhat, rstd per register, h
+__device__ __forceinline__ void ln_forward_tile(const f32x16 (&z)[2], f32x16 (&xh)[2], float (&rs)[16],
+                                                f32x16 (&hout)[2], const float* g, const float* be, int c) {
     const float g0 = g[c], g1 = g[TS + c], b0 = be[c], b1 = be[TS + c];
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
@@ -129,10 +97,10 @@ __device__ __forceinline__ void ln_forward_tile(f32x16 (&z)[2], float (&rs)[16],
         const float var = half32_sum(fmaf(d0, d0, d1 * d1)) * (1.f / 64.f);
         const float rr = rsqrt_nr(var + 1e-5f);
         rs[r] = rr;
-        z[0][r] = d0 * rr;
-        z[1][r] = d1 * rr;
-        hout[0][r] = tanh_fast(fmaf(z[0][r], g0, b0));
-        hout[1][r] = tanh_fast(fmaf(z[1][r], g1, b1));
+        xh[0][r] = d0 * rr;
+        xh[1][r] = d1 * rr;
+        hout[0][r] = tanh_fast(fmaf(xh[0][r], g0, b0));
+        hout[1][r] = tanh_fast(fmaf(xh[1][r], g1, b1));
     }
 }
 // Backward of the same: dh (two column tiles) -> dz (in place); accumulates the per-lane gamma / beta gradients
@@ -162,267 +130,87 @@ __global__ __launch_bounds__(MT) void ppo_update_ln_kernel(LnArgs a) {
     using Sm = LnSmem<O, A, K>;
     auto& S = *reinterpret_cast<Sm*>(smem_raw);
     constexpr int Q = qmax<A, K>();
-    constexpr int KS1 = (O + 1) / 2;  // k-steps of layer 1
     constexpr int IMG = Sm::IMG, NC = Sm::NC, RW = Sm::RW;
-    constexpr int oW2 = O * H, oWh = oW2 + H * SCR, oG1 = oWh + Q * H, oBe1 = oG1 + H, oG2 = oBe1 + H, oBe2 = oG2 + H,
-                  oBh = oBe2 + H, oLs = oBh + Q;
+    constexpr int oG1 = O * H + H * SCR + Q * H, oBe1 = oG1 + H, oG2 = oBe1 + H, oBe2 = oG2 + H, oBh = oBe2 + H,
+                  oLs = oBh + Q;
+    constexpr int cLp = O + A, cAdv = O + A + 1, cV = O + A + 2, cR = O + A + 2 + K;  // columns of a gathered row
     const int t = threadIdx.x, w = t >> 6, l = t & 63, h = l >> 5, c = l & 31;
-    const int bx = (int)blockIdx.x;
-    const int p = 8 * (bx >> 4) + (bx & 7);
-    if (p >= a.P) return;
-    const int m = (bx >> 3) & 1;  // tower: 0 critic, 1 actor
+    int p, m;
+    if (!tower_block(a.P, p, m)) return;
+    const TowerTask<LnArgs> k(a, p, m, O, A, K);
     const int NQ = m == 0 ? K : A;
-    const int N = a.N, T = a.T, B = T * N, BV = (T + 1) * N;
-    const int E = a.hp.ppo_epoch, M = a.hp.num_mini_batch;
-    const int mb = B / M, nb = B / mb;
-    const float clip = a.hp.clip_param;
-    const LayoutLN& L = a.L;
-    float* __restrict__ P = a.params + (size_t)p * L.total;
-    float* __restrict__ Mo = a.m + (size_t)p * L.total;
-    float* __restrict__ Vo = a.v + (size_t)p * L.total;
-    const float* obs = a.obs + (size_t)p * BV * O;
-    const float* actions = a.actions + (size_t)p * B * A;
-    const float* logp = a.logp + (size_t)p * B;
-    const float* advs = a.adv + (size_t)p * B;
-    const float* values = a.values + (size_t)p * BV * K;
-    const float* returns = a.returns + (size_t)p * BV * K;
 
-    // ---- parameter and Adam moment images from the flat HBM vectors
-    float* Pf = &S.Pm.W1t[0][0];
-    if (t < A) S.aiv[t] = expf(-2.f * P[L.off[PGM_PL_LOGSTD] + t]);
-    for (int i = t; i < IMG; i += MT) {
-        const int f = ln_img_to_flat<O, A, K>(i, m, L);
-        Pf[i] = f >= 0 ? P[f] : 0.f;
-        S.MV[i] = f >= 0 ? Mo[f] : 0.f;
-        S.MV[IMG + i] = f >= 0 ? Vo[f] : 0.f;
-    }
-    __syncthreads();
     auto& W = S.Pm;
+    float* Pf = &W.W1t[0][0];
+    auto to_flat = [&](int i) { return ln_img_to_flat<O, A, K>(i, m, a.L); };
+    if (t < A) S.aiv[t] = expf(-2.f * k.P[a.L.off[PGM_PL_LOGSTD] + t]);
+    tower_img_load<IMG>(Pf, S.MV, k, to_flat);
     const float* lstd = W.logstd;  // critic: zeros, unused
 
-    const int step0 = a.step[p];
-    const double lr = a.lr[p];
-    const float b1c = a.hp.beta1, b2c = a.hp.beta2, eps = a.hp.adam_eps;
-    const float vscale = a.hp.value_loss_coef * 0.5f / (float)(mb * K);
-    const float ascale = -1.f / (float)mb;
-    const float vstat = 0.5f / (float)(mb * K), astat = 1.f / (float)mb;  // loss statistics scales
     float st_v = 0.f, st_a = 0.f, st_e = 0.f;
     int nstep = 0;
-    double b1p = pow((double)b1c, (double)step0), b2p = pow((double)b2c, (double)step0);
+    AdamScalars adam(k.b1, k.b2, k.step0);
     float* scr = &S.big.scr[w][0][0];
     float* rt = &S.rows[w][0][0];
-    auto rowf = [&](int cs, int k) { return rt[cs * RW + k]; };
-    float* G = S.big.G;
+    const float* row = rt + c * RW;  // this lane's sample
     PGM_STAMP_DECL
 
-    for (int e = 0; e < E; ++e) {
-        const int32_t* perm = a.perms + (size_t)e * B;
-        for (int bb = 0; bb < nb; ++bb) {
-            f32x16 gW2[2][2], gW1[2];  // [in tile][out tile], [out tile] (O <= 32: one in tile)
-            float gWh[2][Q], gG1[2], gBe1[2], gG2[2], gBe2[2];
-            float gsm = 0.f;  // lanes q < Q: head-bias gradient q; lanes 32 + q (actor): logstd gradient q
-#pragma unroll
-            for (int i = 0; i < 2; ++i) {
-#pragma unroll
-                for (int j = 0; j < 2; ++j) gW2[i][j] = f32x16{0};
-                gW1[i] = f32x16{0};
-                gG1[i] = gBe1[i] = gG2[i] = gBe2[i] = 0.f;
-#pragma unroll
-                for (int q = 0; q < Q; ++q) gWh[i][q] = 0.f;
-            }
+    for (int e = 0; e < k.E; ++e) {
+        for (int bb = 0; bb < k.nb; ++bb) {
+            const int32_t* perm = a.perms + (size_t)e * k.B + bb * k.mb;
+            TowerGrads<Q> g{};
+            float gG1[2] = {0.f, 0.f}, gBe1[2] = {0.f, 0.f}, gG2[2] = {0.f, 0.f}, gBe2[2] = {0.f, 0.f};
+            float gls = 0.f;  // lanes 32 + q (actor): logstd gradient q
             float lsum = 0.f;
 
-            for (int tile = w; tile * TS < mb; tile += 4) {
-                const int ts0 = tile * TS;
-                // ---- gather the tile's samples: lane (h, c) fills half h of sample c's columns; rows past the
-                // minibatch are zero inputs
-                {
-                    const bool okr = ts0 + c < mb;
-                    const int idx = okr ? perm[bb * mb + ts0 + c] : 0;
-                    for (int k = h; k < NC; k += 2) {
-                        float x = 0.f;
-                        if (okr) {
-                            if (k < O) x = obs[(size_t)idx * O + k];
-                            else if (k < O + A) x = actions[(size_t)idx * A + (k - O)];
-                            else if (k == O + A) x = logp[idx];
-                            else if (k == O + A + 1) x = advs[idx];
-                            else if (k < O + A + 2 + K) x = values[(size_t)idx * K + (k - O - A - 2)];
-                            else x = returns[(size_t)idx * K + (k - O - A - 2 - K)];
-                        }
-                        rt[c * RW + k] = x;
-                    }
-                }
-                wave_lds_fence();
+            for (int tile = w; tile * TS < k.mb; tile += 4) {
+                const bool ok = tower_gather_tile<NC, RW>(rt, perm, tile * TS, k.mb, h, c, [&](int idx, int col) {
+                    if (col < O) return k.obs[(size_t)idx * O + col];
+                    if (col < cLp) return k.actions[(size_t)idx * A + (col - O)];
+                    if (col == cLp) return k.logp[idx];
+                    if (col == cAdv) return k.adv[idx];
+                    if (col < cR) return k.values[(size_t)idx * K + (col - cV)];
+                    return k.returns[(size_t)idx * K + (col - cR)];
+                });
                 PGM_STAMP(0);
-                // ---- layer 1: Z1[s][u] = X[s][:] . W1t[:][u]
-                f32x16 z[2] = {f32x16{0}, f32x16{0}};
-#pragma unroll
-                for (int ks = 0; ks < KS1; ++ks) {
-                    const int k = 2 * ks + h;
-                    const float av = k < O ? rowf(c, k) : 0.f;
-#pragma unroll
-                    for (int hb = 0; hb < 2; ++hb) z[hb] = mfma(av, k < O ? W.W1t[k][hb * TS + c] : 0.f, z[hb]);
-                }
-                f32x16 X1[2], H1[2];  // xhat and tanh output of layer 1
-                float rs1[16];
-                ln_forward_tile(z, rs1, H1, W.g1, W.be1, c);
-                X1[0] = z[0];
-                X1[1] = z[1];
-#pragma unroll
-                for (int hb = 0; hb < 2; ++hb)
-#pragma unroll
-                    for (int r = 0; r < 16; ++r) scr[rowof(r, h) * SCR + hb * TS + c] = H1[hb][r];
-                wave_lds_fence();
-                // ---- layer 2: Z2[s][o] = H1[s][:] . W2t[:][o]   (A from the transpose tile)
-                z[0] = z[1] = f32x16{0};
-#pragma unroll 8
-                for (int ks = 0; ks < H / 2; ++ks) {
-                    const int k = 2 * ks + h;
-                    const float av = scr[c * SCR + k];
-#pragma unroll
-                    for (int ob = 0; ob < 2; ++ob) z[ob] = mfma(av, W.W2t[k][ob * TS + c], z[ob]);
-                }
-                f32x16 X2[2], H2[2];
-                float rs2[16];
-                ln_forward_tile(z, rs2, H2, W.g2, W.be2, c);
-                X2[0] = z[0];
-                X2[1] = z[1];
-                PGM_STAMP(4);
-                wave_lds_fence();  // every lane finished reading the H1 tile
-#pragma unroll
-                for (int ob = 0; ob < 2; ++ob)
-#pragma unroll
-                    for (int r = 0; r < 16; ++r) scr[rowof(r, h) * SCR + ob * TS + c] = H2[ob][r];
-                wave_lds_fence();
-                // ---- heads on the VALU: lane = sample c, half h sums units [32h, 32h+32)
-                float outv[Q];
-#pragma unroll
-                for (int q = 0; q < Q; ++q) outv[q] = 0.f;
-#pragma unroll 8
-                for (int u = 0; u < TS; ++u) {
-                    const float hv = scr[c * SCR + h * TS + u];
-#pragma unroll
-                    for (int q = 0; q < Q; ++q) outv[q] = fmaf(hv, W.Wh[q][h * TS + u], outv[q]);
-                }
-#pragma unroll
-                for (int q = 0; q < Q; ++q) outv[q] = half_sum(outv[q]) + W.bh[q];
+                f32x16 X1[2], H1[2], X2[2], H2[2];  // xhat and tanh output of the two layers
+                float rs1[16], rs2[16], outv[Q];
+                tower_forward_tile<O, Q, RW>(
+                    rt, scr, W, h, c, H1, H2, outv,
+                    [&](const f32x16(&z)[2], f32x16(&ho)[2]) { ln_forward_tile(z, X1, rs1, ho, W.g1, W.be1, c); },
+                    [&](const f32x16(&z)[2], f32x16(&ho)[2]) { ln_forward_tile(z, X2, rs2, ho, W.g2, W.be2, c); });
                 PGM_STAMP(16);
                 // ---- per-sample loss gradients (ppo.py:80-96); both halves compute the same sample
-                const bool ok = ts0 + c < mb;
-                float dO[Q];
-#pragma unroll
-                for (int q = 0; q < Q; ++q) dO[q] = 0.f;
+                float dO[Q] = {};
                 if (m == 0) {  // value loss
-                    float ls = 0.f;
-#pragma unroll
-                    for (int q = 0; q < K; ++q) {
-                        const float V = outv[q], Vold = rowf(c, O + A + 2 + q);
-                        const float R = rowf(c, O + A + 2 + K + q);
-                        float gv;
-                        if (a.hp.use_clipped_value_loss) {
-                            const float dv = V - Vold;
-                            const float vc = Vold + fminf(fmaxf(dv, -clip), clip);
-                            const float l1 = (V - R) * (V - R), l2 = (vc - R) * (vc - R);
-                            const float inr = (dv >= -clip && dv <= clip) ? 1.f : 0.f;
-                            gv = wmax2(l1, l2) * 2.f * (V - R) + wmax2(l2, l1) * 2.f * (vc - R) * inr;
-                            ls += fmaxf(l1, l2);
-                        } else {
-                            gv = 2.f * (V - R);
-                            ls += (R - V) * (R - V);
-                        }
-                        dO[q] = ok ? vscale * gv : 0.f;
-                    }
+                    const float ls = tower_value_loss<K>(dO, outv, row + cV, row + cR, k.clip,
+                                                         a.hp.use_clipped_value_loss, ok, k.vscale);
                     if (ok && h == 0) lsum += ls;
-                } else {  // clipped surrogate
+                } else {  // diagonal Gaussian log-prob, clipped surrogate
                     float lp = 0.f;
 #pragma unroll
                     for (int q = 0; q < A; ++q) {
-                        const float diff = rowf(c, O + q) - outv[q];
+                        const float diff = row[O + q] - outv[q];
                         lp += -0.5f * diff * diff * S.aiv[q] - lstd[q] - LOG_SQRT_2PI;
                     }
-                    const float ratio = expf(lp - rowf(c, O + A));
-                    const float ad = rowf(c, O + A + 1);
-                    const float s1 = ratio * ad;
-                    const float s2 = fminf(fmaxf(ratio, 1.f - clip), 1.f + clip) * ad;
-                    const float inr = (ratio >= 1.f - clip && ratio <= 1.f + clip) ? 1.f : 0.f;
-                    const float gr = ad * (wmin2(s1, s2) + wmin2(s2, s1) * inr);
-                    const float dlp = ok ? ascale * gr * ratio : 0.f;
-                    if (ok && h == 0) lsum += -fminf(s1, s2);
+                    const float ratio = expf(lp - row[cLp]);
+                    const LossTerm sg = surrogate_term(ratio, row[cAdv], k.clip);
+                    const float dlp = ok ? k.ascale * sg.grad * ratio : 0.f;
+                    if (ok && h == 0) lsum += sg.loss;
 #pragma unroll
                     for (int q = 0; q < A; ++q) {
-                        const float diff = rowf(c, O + q) - outv[q];
+                        const float diff = row[O + q] - outv[q];
                         const float iv = S.aiv[q];
                         dO[q] = dlp * diff * iv;
                         if (h == 0) S.dls[w][c][q] = dlp * (diff * diff * iv - 1.f);
                     }
                 }
-                if (h == 0) {
-#pragma unroll
-                    for (int q = 0; q < Q; ++q) S.dout[w][c][q] = dO[q];
-                }
                 PGM_STAMP(17);
-                wave_lds_fence();
-                // per-column sums of the tile: lane q sums dO[.][q], lane 32 + q the logstd terms
-                if (c < (h == 0 ? Q : (m == 1 ? A : 0))) {
-                    const float* src = (h == 0 ? &S.dout[w][0][0] : &S.dls[w][0][0]) + c;
-#pragma unroll 8
-                    for (int cc = 0; cc < TS; ++cc) gsm += src[cc * Q];
-                }
-                PGM_STAMP(5);
-                // ---- head-weight grads (VALU, C layout): gWh[ob][q] += sum_r H2[s][u] dO[s][q]
-#pragma unroll
-                for (int ob = 0; ob < 2; ++ob)
-#pragma unroll
-                    for (int r = 0; r < 16; ++r) {
-                        const int s = rowof(r, h);
-#pragma unroll
-                        for (int q = 0; q < Q; ++q) gWh[ob][q] = fmaf(H2[ob][r], S.dout[w][s][q], gWh[ob][q]);
-                    }
-                // ---- dH2 = dO . Wh  (MFMA; A = this lane's sample, k = head output)
-                z[0] = z[1] = f32x16{0};
-#pragma unroll
-                for (int ks = 0; ks < (Q + 1) / 2; ++ks) {
-                    const int q = 2 * ks + h;
-                    const float av = h ? (2 * ks + 1 < Q ? dO[2 * ks + 1] : 0.f) : dO[2 * ks];
-#pragma unroll
-                    for (int ob = 0; ob < 2; ++ob) z[ob] = mfma(av, q < Q ? W.Wh[q][ob * TS + c] : 0.f, z[ob]);
-                }
-                // ---- LayerNorm 2 backward: dH2 -> dZ2 (in z), dgamma2 / dbeta2
-                ln_backward_tile(z, H2, X2, rs2, W.g2, c, gG2, gBe2);
-                f32x16 dZ2[2] = {z[0], z[1]};
-                PGM_STAMP(6);
-                // ---- dH1 = dZ2 W2  (A = dZ2 through the transpose tile, B = W2t[in][o] column)
-                wave_lds_fence();  // heads finished reading the H2 tile
-#pragma unroll
-                for (int ob = 0; ob < 2; ++ob)
-#pragma unroll
-                    for (int r = 0; r < 16; ++r) scr[rowof(r, h) * SCR + ob * TS + c] = dZ2[ob][r];
-                wave_lds_fence();
-                z[0] = z[1] = f32x16{0};
-#pragma unroll 8
-                for (int ks = 0; ks < H / 2; ++ks) {
-                    const int k = 2 * ks + h;  // output unit o
-                    const float av = scr[c * SCR + k];
-#pragma unroll
-                    for (int ib = 0; ib < 2; ++ib) z[ib] = mfma(av, W.W2t[ib * TS + c][k], z[ib]);
-                }
-                // ---- dW2^T[in][o] += H1^T dZ2: straight from the C-layout registers
-#pragma unroll
-                for (int r = 0; r < 16; ++r)
-#pragma unroll
-                    for (int ib = 0; ib < 2; ++ib)
-#pragma unroll
-                        for (int ob = 0; ob < 2; ++ob) gW2[ib][ob] = mfma(H1[ib][r], dZ2[ob][r], gW2[ib][ob]);
-                // ---- LayerNorm 1 backward: dH1 -> dZ1 (in z), dgamma1 / dbeta1
-                ln_backward_tile(z, H1, X1, rs1, W.g1, c, gG1, gBe1);
-                // ---- dW1^T[k][u] += X^T dZ1  (A = X[s(r)][k = lane], B = dZ1 reg r)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) {
-                    const float av = c < O ? rowf(rowof(r, h), c) : 0.f;
-#pragma unroll
-                    for (int hb = 0; hb < 2; ++hb) gW1[hb] = mfma(av, z[hb][r], gW1[hb]);
-                }
-                wave_lds_fence();  // dH1 finished reading the dZ2 tile, dW1 the rows, before the next tile's writes
+                tower_backward_tile<O, Q, RW>(
+                    g, dO, &S.dout[w][0][0], rt, scr, W, H1, H2, h, c,
+                    [&](f32x16(&z)[2], const f32x16(&hv)[2]) { ln_backward_tile(z, hv, X2, rs2, W.g2, c, gG2, gBe2); },
+                    [&](f32x16(&z)[2], const f32x16(&hv)[2]) { ln_backward_tile(z, hv, X1, rs1, W.g1, c, gG1, gBe1); });
+                if (h == 1 && m == 1 && c < A) tile_col_add<Q>(gls, &S.dls[w][0][0] + c);
                 PGM_STAMP(7);
             }  // tiles
 
@@ -433,135 +221,40 @@ __global__ __launch_bounds__(MT) void ppo_update_ln_kernel(LnArgs a) {
                 gBe1[i] = half_sum(gBe1[i]);
                 gG2[i] = half_sum(gG2[i]);
                 gBe2[i] = half_sum(gBe2[i]);
-#pragma unroll
-                for (int q = 0; q < Q; ++q) gWh[i][q] = half_sum(gWh[i][q]);
             }
             lsum = wave_sum64(lsum);
-            // entropy with the logstd of this step (before Adam)
-            float ent = 0.f;
-#pragma unroll
-            for (int q = 0; q < A; ++q) ent += 0.5f + LOG_SQRT_2PI + lstd[q];
             if (l == 0) S.red[8 + w] = lsum;
             lds_sync_m();  // every wave's tiles done: the gradient image overwrites the transpose tiles
             PGM_STAMP(12);
-
-            // ---- gradient image: wave 0 stores its partials (and the zeros of the padding slots), waves 1..3 add
-            // theirs in order, one barrier per round: every element is ((w0 + w1) + w2) + w3, deterministic
-            for (int round = 0; round < 4; ++round) {
-                if (w == round) {
-                    const bool add = round != 0;
-                    auto acc = [&](int idx, float val) { G[idx] = add ? G[idx] + val : val; };
-#pragma unroll
-                    for (int i = 0; i < 2; ++i) {
-#pragma unroll
-                        for (int ob = 0; ob < 2; ++ob)
-#pragma unroll
-                            for (int r = 0; r < 16; ++r)
-                                acc(oW2 + (i * TS + rowof(r, h)) * SCR + ob * TS + c, gW2[i][ob][r]);
-#pragma unroll
-                        for (int r = 0; r < 16; ++r) {  // rows k >= O of dW1 are exactly zero (A operand 0)
-                            const int k = rowof(r, h);
-                            if (k < O) acc(k * H + i * TS + c, gW1[i][r]);
-                        }
-                        if (h == 0) {  // per-unit sums of unit block i
-                            acc(oG1 + i * TS + c, gG1[i]);
-                            acc(oBe1 + i * TS + c, gBe1[i]);
-                            acc(oG2 + i * TS + c, gG2[i]);
-                            acc(oBe2 + i * TS + c, gBe2[i]);
-#pragma unroll
-                            for (int q = 0; q < Q; ++q) acc(oWh + q * H + i * TS + c, q < NQ ? gWh[i][q] : 0.f);
-                        }
-                    }
-                    if (h == 0 && c < Q) acc(oBh + c, c < NQ ? gsm : 0.f);
-                    if (h == 1 && c < A) {  // -entropy_coef * d(mean entropy)/d logstd enters once (ppo.py:98)
-                        acc(oLs + c, m == 1 ? gsm - (add ? 0.f : a.hp.entropy_coef) : 0.f);
-                    }
-                    if (!add) G[oW2 + l * SCR + H] = 0.f;  // W2 padding column
-                }
-                lds_sync_m();
-            }
+            tower_reduce_image<O, Q>(
+                S.big.G, g, NQ, oBh,
+                [&](auto acc, int i) {
+                    acc(oG1 + i * TS + c, gG1[i]);
+                    acc(oBe1 + i * TS + c, gBe1[i]);
+                    acc(oG2 + i * TS + c, gG2[i]);
+                    acc(oBe2 + i * TS + c, gBe2[i]);
+                },
+                [&](auto acc, bool add) {  // -entropy_coef * d(mean entropy)/d logstd enters once (ppo.py:98)
+                    if (h == 1 && c < A) acc(oLs + c, m == 1 ? gls - (add ? 0.f : a.hp.entropy_coef) : 0.f);
+                });
             PGM_STAMP(2);
-            // ---- clip_grad_norm_ over every parameter (padding slots hold zeros)
-            float sq = 0.f;
-            for (int i = t; i < IMG; i += MT) sq = fmaf(G[i], G[i], sq);
-            sq = wave_sum64(sq);
-            if (l == 0) S.red[w] = sq;
-            lds_sync_m();
-            PGM_STAMP(8);
-            float total = (S.red[0] + S.red[1]) + (S.red[2] + S.red[3]);
-            if (t == 0) {  // tagged 8-byte granule hand-off with the other tower's workgroup
-                const unsigned tag = (unsigned)(nstep + 1);
-                unsigned long long* ws = a.ws + ppo_norm_granule(a.P, p, 0, 0, nstep & 1);
-                __hip_atomic_store(ws + m, ((unsigned long long)tag << 32) | __float_as_uint(total), __ATOMIC_RELAXED,
-                                   __HIP_MEMORY_SCOPE_AGENT);
-                dbg_delay(a.dbg, nstep, 2);
-                unsigned long long x = 0;
-                const bool failed = __hip_atomic_load(a.ws + 2 * a.P, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                for (unsigned spins = 0; !failed; ++spins) {
-                    x = __hip_atomic_load(ws + (1 - m), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    if ((unsigned)(x >> 32) == tag) break;
-                    if (spins > (1u << 26)) {  // partner never arrived: flag the launch as failed
-                        __hip_atomic_store(a.ws + 2 * a.P, 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                        x = 0;
-                        break;
-                    }
-                    __builtin_amdgcn_s_sleep(1);
-                }
-                const float other = __uint_as_float((unsigned)x);
-                S.red[4] = m == 0 ? total + other : other + total;  // critic + actor in both workgroups
-            }
-            lds_sync_m();
-            total = S.red[4];
-            PGM_STAMP(9);
-            const float coef = clip_coef(a.hp.max_grad_norm, total);
             if (t == 0) {
-                const float ls = (S.red[8] + S.red[9]) + (S.red[10] + S.red[11]);
-                if (m == 0) st_v += ls * vstat;
-                else st_a += ls * astat;
+                const float ls = sum4(S.red + 8);
+                if (m == 0) st_v += ls * k.vstat;
+                else st_a += ls * k.astat;
+                float ent = 0.f;  // entropy with the logstd of this step (before Adam)
+#pragma unroll
+                for (int q = 0; q < A; ++q) ent += 0.5f + LOG_SQRT_2PI + lstd[q];
                 st_e += ent;
             }
-            // ---- Adam, one flat pass over the images (padding: g = m = v = 0 keeps p = 0)
-            ++nstep;
-            const double b1n = b1p * (double)b1c, b2n = b2p * (double)b2c;
-            const float step_size = (float)(lr / (1.0 - b1n));
-            const float inv_bc2s = 1.f / (float)sqrt(1.0 - b2n);
-            b1p = b1n;
-            b2p = b2n;
-            for (int i = t; i < IMG; i += MT) {
-                const float gc = G[i] * coef;
-                float mm = S.MV[i], vv = S.MV[IMG + i], pp = Pf[i];
-                mm = mm + (1.f - b1c) * (gc - mm);
-                vv = vv * b2c + (1.f - b2c) * (gc * gc);
-                // torch: p -= step_size * m / (sqrt(v) / sqrt(bc2) + eps); hardware sqrt / rcp
-                const float den = __builtin_amdgcn_sqrtf(vv) * inv_bc2s + eps;
-                pp -= step_size * mm * __builtin_amdgcn_rcpf(den);
-                S.MV[i] = mm;
-                S.MV[IMG + i] = vv;
-                Pf[i] = pp;
+            tower_clip_adam<IMG>(S.big.G, S.MV, Pf, S.red, a, k, nstep, adam, [&](int i, float pp) {
                 if (m == 1 && i >= oLs && i < oLs + A) S.aiv[i - oLs] = expf(-2.f * pp);
-            }
-            lds_sync_m();  // parameters updated before the next minibatch; G region reused as transpose tiles
+            });
             PGM_STAMP(3);
         }  // minibatches
     }      // epochs
-    // ---- write back the parameters and the moments
-    for (int i = t; i < IMG; i += MT) {
-        const int f = ln_img_to_flat<O, A, K>(i, m, L);
-        if (f < 0) continue;
-        P[f] = Pf[i];
-        Mo[f] = S.MV[i];
-        Vo[f] = S.MV[IMG + i];
-    }
-    if (t == 0) {
-        const float n = (float)(E * M);
-        if (m == 0) {
-            a.stats[p * 3 + 0] = st_v / n;
-        } else {
-            a.step[p] = step0 + nstep;
-            a.stats[p * 3 + 1] = st_a / n;
-            a.stats[p * 3 + 2] = st_e / n;
-        }
-    }
+    tower_img_store<IMG>(Pf, S.MV, k, to_flat);
+    if (t == 0) tower_write_stats(a, k, nstep, st_v, st_a, st_e);
     PGM_STAMP_FLUSH;
 }
 
@@ -585,28 +278,10 @@ int ppo_update_ln(const pgm_dims* d, const pgm_ppo_hparams* hp, float* params, f
             set_error("pgm_ppo_update: LayerNorm towers need obs_dim <= 32 (got %d)", O);
             return PGM_E_UNSUPPORTED;
         } else {
-            constexpr size_t smem = sizeof(LnSmem<O, A, K>);
-            static_assert(smem <= 160 * 1024, "LayerNorm update LDS image exceeds 160 KiB");
-            static_assert(smem > 80 * 1024, "one workgroup per CU: the residency argument needs > 80 KiB LDS");
-            const int cus = device_cu_count();
-            if (2 * d->P > cus) {
-                set_error("pgm_ppo_update: the LayerNorm update runs one workgroup per tower and needs 2 P = %d <= %d "
-                          "CUs; shard the tasks over more GPUs", 2 * d->P, cus);
-                return PGM_E_UNSUPPORTED;
-            }
-            auto kern = ppo_update_ln_kernel<O, A, K>;
-            hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-            if (e != hipSuccess) return hip_fail(e, "pgm_ppo_update");
-            // the workgroups exchange through spin-waits: the 2 P working ones must be resident together (the
-            // padding blocks of the last group exit at once)
-            if (int rc = check_coresident((const void*)kern, MT, smem, 2 * d->P, "pgm_ppo_update")) return rc;
-            const size_t zb = ppo_flag_bytes(d->P);  // norm granules + timeout word start at tag 0
-            if (!ws_take_zeroed(a.ws, zb)) {
-                e = hipMemsetAsync(a.ws, 0, zb, stream);
-                if (e != hipSuccess) return hip_fail(e, "pgm_ppo_update (workspace reset)");
-            }
-            hipLaunchKernelGGL(kern, dim3(ln_grid(d->P)), dim3(MT), smem, stream, a);
-            return launch_status("pgm_ppo_update");
+            return launch_tower_update<sizeof(LnSmem<O, A, K>)>(
+                ppo_update_ln_kernel<O, A, K>, a, stream, "pgm_ppo_update",
+                "pgm_ppo_update: the LayerNorm update runs one workgroup per tower and needs 2 P = %d <= %d "
+                "CUs; shard the tasks over more GPUs");
         }
     });
 }

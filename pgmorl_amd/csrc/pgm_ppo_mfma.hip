@@ -266,7 +266,7 @@ __global__ __launch_bounds__(MT) void ppo_update_mfma_kernel(MArgs a) {
             // 1 / sqrt(bias correction 2); MODE 2 forms them while its image stores drain
             double b1n = 0.0, b2n = 0.0;
             float step_size = 0.f, inv_bc2s = 0.f;
-            auto adam_scalars = [&]() {
+            auto adam_scalars = [&]() {  // restates AdamScalars::advance (pgm_ppo_terms.hpp): moving it changes this file's register allocation
                 b1n = b1p * (double)b1c;
                 b2n = b2p * (double)b2c;
                 step_size = (float)(lr / (1.0 - b1n));
@@ -372,21 +372,11 @@ PGM_UNROLL(16)
                         float ls = 0.f;
 #pragma unroll
                         for (int q = 0; q < K; ++q) {
-                            const float V = outv[q], Vo = rowf(rt, c, O + A + 2 + q);
-                            const float R = rowf(rt, c, O + A + 2 + K + q);
-                            float gv;
-                            if (a.hp.use_clipped_value_loss) {
-                                const float dv = V - Vo;
-                                const float vc = Vo + fminf(fmaxf(dv, -clip), clip);
-                                const float l1 = (V - R) * (V - R), l2 = (vc - R) * (vc - R);
-                                const float inr = (dv >= -clip && dv <= clip) ? 1.f : 0.f;
-                                gv = wmax2(l1, l2) * 2.f * (V - R) + wmax2(l2, l1) * 2.f * (vc - R) * inr;
-                                ls += fmaxf(l1, l2);
-                            } else {
-                                gv = 2.f * (V - R);
-                                ls += (R - V) * (R - V);
-                            }
-                            dO[q] = ok ? vscale * gv : 0.f;
+                            const LossTerm vl = value_loss_term(outv[q], rowf(rt, c, O + A + 2 + q),
+                                                                rowf(rt, c, O + A + 2 + K + q), clip,
+                                                                a.hp.use_clipped_value_loss);
+                            ls += vl.loss;
+                            dO[q] = ok ? vscale * vl.grad : 0.f;
                         }
                         if (ok && h == 0) lsum += ls;
                     } else {  // clipped surrogate
@@ -397,6 +387,7 @@ PGM_UNROLL(16)
                             lp += -0.5f * diff * diff * S.aiv[q] - lstd[q] - LOG_SQRT_2PI;
                         }
                         const float ratio = expf(lp - rowf(rt, c, O + A));
+                        // restates surrogate_term (pgm_ppo_terms.hpp): moving it changes this file's register allocation
                         const float ad = rowf(rt, c, O + A + 1);
                         const float s1 = ratio * ad;
                         const float s2 = fminf(fmaxf(ratio, 1.f - clip), 1.f + clip) * ad;
@@ -676,6 +667,7 @@ PGM_UNROLL(ONE ? PGM_U_L2 : 8)
                     const int pslot = t == 0 ? slot_other : slot_t0 + 2 * (t - 1);
                     const unsigned long long* flag_p = a.xb + (size_t)pslot * a.xslot + a.xslot - 1;
                     unsigned long long x = 0;
+                    // restates poll_tagged (pgm_ppo_terms.hpp): moving it changes this file's register allocation
                     for (unsigned spins = 0;; ++spins) {
                         x = __hip_atomic_load(flag_p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                         if ((unsigned)(x >> 32) == tag) break;
@@ -781,7 +773,7 @@ PGM_UNROLL(ONE ? PGM_U_L2 : 8)
                 const float other = (S.red[4] + S.red[5]) + (S.red[6] + S.red[7]);
                 total = m == 0 ? total + other : other + total;  // critic + actor in all four workgroups
             } else if constexpr (SPLIT) {  // tagged 8-byte granule hand-off with the other tower's workgroup
-                if (t == 0) {
+                if (t == 0) {  // restates tower_norm_exchange (pgm_ppo_terms.hpp): moving it changes this file's register allocation
                     const unsigned tag = (unsigned)(nstep + 1);
                     unsigned long long* ws = a.ws + ppo_norm_granule(a.P, p, 0, hs, nstep & 1);
                     __hip_atomic_store(ws + m, ((unsigned long long)tag << 32) | __float_as_uint(total),
@@ -824,12 +816,7 @@ PGM_UNROLL(ONE ? PGM_U_L2 : 8)
             b1p = b1n;
             b2p = b2n;
             auto adam1 = [&](float g, float& mm, float& vv, float& pp) {
-                const float gc = g * coef;
-                mm = mm + (1.f - b1c) * (gc - mm);
-                vv = vv * b2c + (1.f - b2c) * (gc * gc);
-                // torch: p -= step_size * m / (sqrt(v) / sqrt(bc2) + eps); hardware sqrt / rcp
-                const float den = __builtin_amdgcn_sqrtf(vv) * inv_bc2s + eps;
-                pp -= step_size * mm * __builtin_amdgcn_rcpf(den);
+                adam_step(g, coef, mm, vv, pp, b1c, b2c, step_size, inv_bc2s, eps);
             };
             if constexpr (NS == 2) {  // operands already in registers (float4 groups of the gather)
 #pragma unroll
@@ -884,13 +871,7 @@ PGM_UNROLL(ONE ? PGM_U_L2 : 8)
                     }
 #pragma unroll
                     for (int j = 0; j < 4; ++j) {
-                        const float gc = g[j] * coef;
-                        mm[j] = mm[j] + (1.f - b1c) * (gc - mm[j]);
-                        vv[j] = vv[j] * b2c + (1.f - b2c) * (gc * gc);
-                        // torch: p -= step_size * m / (sqrt(v) / sqrt(bc2) + eps); hardware sqrt / rcp
-                        // (<= 2 ulp on the step, against an fp64 reference anyway)
-                        const float den = __builtin_amdgcn_sqrtf(vv[j]) * inv_bc2s + eps;
-                        pp[j] -= step_size * mm[j] * __builtin_amdgcn_rcpf(den);
+                        adam_step(g[j], coef, mm[j], vv[j], pp[j], b1c, b2c, step_size, inv_bc2s, eps);
                     }
 #pragma unroll
                     for (int j = 0; j < 4; ++j) {
@@ -1199,20 +1180,9 @@ PGM_UNROLL(ONE ? PGM_U16 : 4)
                             const float V = ho[r] + bh;
                             const float Vold = rt[s * RSL + O + A + 2 + (c < K ? c : 0)];
                             const float R = rt[s * RSL + O + A + 2 + K + (c < K ? c : 0)];
-                            float gv, ls;
-                            if (a.hp.use_clipped_value_loss) {
-                                const float dv = V - Vold;
-                                const float vc = Vold + fminf(fmaxf(dv, -clip), clip);
-                                const float l1 = (V - R) * (V - R), l2 = (vc - R) * (vc - R);
-                                const float inr = (dv >= -clip && dv <= clip) ? 1.f : 0.f;
-                                gv = wmax2(l1, l2) * 2.f * (V - R) + wmax2(l2, l1) * 2.f * (vc - R) * inr;
-                                ls = fmaxf(l1, l2);
-                            } else {
-                                gv = 2.f * (V - R);
-                                ls = (R - V) * (R - V);
-                            }
-                            dO[r] = ok ? vscale * gv : 0.f;
-                            lsum += ok ? ls : 0.f;
+                            const LossTerm vl = value_loss_term(V, Vold, R, clip, a.hp.use_clipped_value_loss);
+                            dO[r] = ok ? vscale * vl.grad : 0.f;
+                            lsum += ok ? vl.loss : 0.f;
                         }
                     } else {  // clipped surrogate; the log-prob of a sample is a row sum over its outputs
                         const bool av_ = c < A;
@@ -1225,6 +1195,7 @@ PGM_UNROLL(ONE ? PGM_U16 : 4)
                             const float lpe = av_ ? -0.5f * diff * diff * aiv - ls_c - LOG_SQRT_2PI : 0.f;
                             const float lp = row_sum16(lpe);
                             const float ratio = expf(lp - rt[s * RSL + O + A]);
+                            // restates surrogate_term (pgm_ppo_terms.hpp): moving it changes this file's register allocation
                             const float ad = rt[s * RSL + O + A + 1];
                             const float s1 = ratio * ad;
                             const float s2 = fminf(fmaxf(ratio, 1.f - clip), 1.f + clip) * ad;
@@ -1489,6 +1460,7 @@ PGM_UNROLL(ONE ? PGM_U16 : 4)
                         if (t != hs) {
                             const unsigned long long* flag_h = a.xb + (size_t)slot_of(t) * a.xslot + a.xslot - 1;
                             unsigned long long x = 0;
+                            // restates poll_tagged (pgm_ppo_terms.hpp): moving it changes this file's register allocation
                             for (unsigned spins = 0;; ++spins) {
                                 x = __hip_atomic_load(flag_h, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                                 if ((unsigned)(x >> 32) == tag) break;
@@ -1624,6 +1596,7 @@ PGM_UNROLL(ONE ? PGM_U16 : 4)
             for (int i = 0; i < W; ++i) total += S.red[i];
             PGM_STAMP(8);
             // this step's Adam scalars (fp64 bias corrections) while the norm granule travels
+            // (restates AdamScalars::advance of pgm_ppo_terms.hpp: moving it changes this file's register allocation)
             const double b1n = b1p * (double)b1c, b2n = b2p * (double)b2c;
             float step_size = (float)(lr / (1.0 - b1n));
             float inv_bc2s = 1.f / (float)sqrt(1.0 - b2n);
@@ -1634,7 +1607,7 @@ PGM_UNROLL(ONE ? PGM_U16 : 4)
                     if (gp + 1 < npass) issue_idx(gp + 1, (gp + 1) & 1, w - 1, W - 1);
                 }
             }
-            if (t == 0) {
+            if (t == 0) {  // restates tower_norm_exchange (pgm_ppo_terms.hpp): moving it changes this file's register allocation
                 const unsigned tag = (unsigned)(nstep + 1);
                 unsigned long long* gr = a.ws + ppo_norm_granule(a.P, p, 0, hs, nstep & 1);
                 __hip_atomic_store(gr + m, ((unsigned long long)tag << 32) | __float_as_uint(total), __ATOMIC_RELAXED,
@@ -1669,11 +1642,7 @@ PGM_UNROLL(ONE ? PGM_U16 : 4)
             b1p = b1n;
             b2p = b2n;
             auto adam1 = [&](float gg, float& mm, float& vv, float& pp) {
-                const float gc = gg * coef;
-                mm = mm + (1.f - b1c) * (gc - mm);
-                vv = vv * b2c + (1.f - b2c) * (gc * gc);
-                const float den = __builtin_amdgcn_sqrtf(vv) * inv_bc2s + eps;
-                pp -= step_size * mm * __builtin_amdgcn_rcpf(den);
+                adam_step(gg, coef, mm, vv, pp, b1c, b2c, step_size, inv_bc2s, eps);
             };
 #pragma unroll
             for (int k = 0; k < NG4; ++k) {
@@ -1746,15 +1715,10 @@ static int launch_t16_k(const pgm_dims* d, const MArgs& a, hipStream_t stream) {
     }
     static_assert(sizeof(Sm) > 80 * 1024, "residency argument (one workgroup per CU) needs > 80 KiB LDS");
     auto kern = ppo_update_t16_kernel<O, A, K, NS, W, ONE>;
-    hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-    if (e != hipSuccess) return hip_fail(e, "pgm_ppo_update");
     const int grid = t16_grid(d->P, NS);
-    if (int rc = check_coresident((const void*)kern, 64 * W, smem, grid, "pgm_ppo_update")) return rc;
     const size_t zb = ppo_flag_bytes(d->P) + ppo_xbuf_bytes(d, NS);
-    if (!ws_take_zeroed(a.ws, zb)) {
-        e = hipMemsetAsync(a.ws, 0, zb, stream);
-        if (e != hipSuccess) return hip_fail(e, "pgm_ppo_update (workspace reset)");
-    }
+    if (int rc = prepare_update_launch((const void*)kern, 64 * W, smem, grid, a.ws, zb, stream, "pgm_ppo_update"))
+        return rc;
     hipLaunchKernelGGL(kern, dim3(grid), dim3(64 * W), smem, stream, a);
     return launch_status("pgm_ppo_update");
 }
@@ -1777,19 +1741,14 @@ int launch_mode_k(const pgm_dims* d, const MArgs& a, hipStream_t stream) {
         return PGM_E_UNSUPPORTED;
     }
     auto kern = ppo_update_mfma_kernel<O, A, K, MODE, ONE>;
-    hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-    if (e != hipSuccess) return hip_fail(e, "pgm_ppo_update");
     // norm granules, timeout flag (and MODE 2: the exchange slots) start at tag 0; MODE 0 resets the flag
     // word too, so word 2P always reports THIS call
     const int grid = MODE == 2 ? mode2_grid(d->P) : SPLIT ? 2 * d->P : d->P;
-    if constexpr (SPLIT) {  // workgroups exchange through spin-waits: all of them must be resident together
-        if (int rc = check_coresident((const void*)kern, MT, smem, grid, "pgm_ppo_update")) return rc;
-    }
     const size_t zb = ppo_flag_bytes(d->P) + (MODE == 2 ? ppo_xbuf_bytes(d) : 0);
-    if (!ws_take_zeroed(a.ws, zb)) {
-        e = hipMemsetAsync(a.ws, 0, zb, stream);
-        if (e != hipSuccess) return hip_fail(e, "pgm_ppo_update (workspace reset)");
-    }
+    // SPLIT workgroups exchange through spin-waits: all of them must be resident together
+    if (int rc = prepare_update_launch((const void*)kern, MT, smem, SPLIT ? grid : 0, a.ws, zb, stream,
+                                       "pgm_ppo_update"))
+        return rc;
     hipLaunchKernelGGL(kern, dim3(grid), dim3(MT), smem, stream, a);
     return launch_status("pgm_ppo_update");
 }

@@ -1,20 +1,10 @@
 // Shared pieces of the obs_dim <= 32 PPO update kernels (pgm_ppo_mfma.hip: MODE 0/1/2 and 16-row tiles;
 // pgm_ppo_fs.hip: feature-split tiles with a reduce-scattered Adam): the LDS tower image, its map to the flat
-// parameter layout, the launch arguments and the clip coefficient.
+// parameter layout and the launch arguments.
 #pragma once
 #include "pgm_mfma.hpp"
 
 namespace pgm {
-
-// clip_grad_norm_'s coefficient min(max_norm / (sqrt(sum of squares) + 1e-6), 1) (torch nn/utils/clip_grad.py):
-// hardware sqrt and a Newton-refined reciprocal (<= 1 ulp) instead of the IEEE expansions, off the critical path's
-// division sequences
-__device__ __forceinline__ float clip_coef(float max_norm, float sumsq) {
-    const float d = __builtin_amdgcn_sqrtf(sumsq) + 1e-6f;
-    float r = __builtin_amdgcn_rcpf(d);
-    r = fmaf(fmaf(-d, r, 1.f), r, r);
-    return fminf(max_norm * r, 1.f);
-}
 
 // ---------------------------------------------------------------- tower images
 // One tower's parameters as an LDS image: W1^T [in][out], W2^T [in][out] with a padded row stride,

@@ -19,6 +19,7 @@
 #include <unordered_map>
 
 #include "pgm_dispatch.hpp"
+#include "pgm_ppo_terms.hpp"
 
 PGM_STAMP_UNIT(update)
 
@@ -79,10 +80,6 @@ __device__ __forceinline__ float block_sum_f(float x, float* red) {
     for (int i = 0; i < UT / 64; ++i) s += red[i];
     return s;
 }
-
-// torch.min(a,b) / torch.max(a,b) backward weights for the first argument (ties: half)
-__device__ __forceinline__ float wmin(float a, float b) { return a < b ? 1.f : (a == b ? 0.5f : 0.f); }
-__device__ __forceinline__ float wmax(float a, float b) { return a > b ? 1.f : (a == b ? 0.5f : 0.f); }
 
 // Adam on one owned element; returns the new parameter value.
 __device__ __forceinline__ float adam_elem(float* P, float* M, float* V, int idx, float g, float b1, float b2,
@@ -299,14 +296,9 @@ __global__ __launch_bounds__(UT) void ppo_update_kernel(UpdArgs a) {
                         lp += -0.5f * dz * dz - S.logstd[q] - LOG_SQRT_2PI;
                     }
                     const float ratio = expf(lp - S.oldlp[r]);
-                    const float ad = S.adv[r];
-                    const float s1 = ratio * ad;
-                    const float rc = fminf(fmaxf(ratio, 1.f - clip), 1.f + clip);
-                    const float s2 = rc * ad;
-                    const float inr = (ratio >= 1.f - clip && ratio <= 1.f + clip) ? 1.f : 0.f;
-                    const float gr = ad * (wmin(s1, s2) + wmin(s2, s1) * inr);   // d min(s1,s2) / d ratio
-                    const float dlp = ok ? ascale * gr * ratio : 0.f;            // dL/dlogp
-                    S.rowloss[r][1] = ok ? -fminf(s1, s2) : 0.f;
+                    const LossTerm sg = surrogate_term(ratio, S.adv[r], clip);
+                    const float dlp = ok ? ascale * sg.grad * ratio : 0.f;  // dL/dlogp
+                    S.rowloss[r][1] = ok ? sg.loss : 0.f;
 #pragma unroll
                     for (int q = 0; q < A; ++q) {
                         const float sd = expf(S.logstd[q]);
@@ -321,20 +313,10 @@ __global__ __launch_bounds__(UT) void ppo_update_kernel(UpdArgs a) {
                     float ls = 0.f;
 #pragma unroll
                     for (int q = 0; q < K; ++q) {
-                        const float V = S.v[r][q], Vo = S.vold[r][q], R = S.ret[r][q];
-                        float gv;
-                        if (a.hp.use_clipped_value_loss) {
-                            const float dv = V - Vo;
-                            const float vc = Vo + fminf(fmaxf(dv, -clip), clip);
-                            const float l1 = (V - R) * (V - R), l2 = (vc - R) * (vc - R);
-                            const float inr = (dv >= -clip && dv <= clip) ? 1.f : 0.f;
-                            gv = wmax(l1, l2) * 2.f * (V - R) + wmax(l2, l1) * 2.f * (vc - R) * inr;
-                            ls += fmaxf(l1, l2);
-                        } else {
-                            gv = 2.f * (V - R);
-                            ls += (R - V) * (R - V);
-                        }
-                        S.v[r][q] = ok ? vscale * gv : 0.f;  // dL/dV
+                        const LossTerm vl = value_loss_term(S.v[r][q], S.vold[r][q], S.ret[r][q], clip,
+                                                            a.hp.use_clipped_value_loss);
+                        ls += vl.loss;
+                        S.v[r][q] = ok ? vscale * vl.grad : 0.f;  // dL/dV
                     }
                     S.rowloss[r][0] = ok ? ls : 0.f;
                 }

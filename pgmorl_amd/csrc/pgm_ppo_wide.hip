@@ -239,7 +239,7 @@ __global__ __launch_bounds__(MT) void ppo_update_wide_kernel(WArgs a) {
     const float ascale = -1.f / (float)mb;
     float st_v = 0.f, st_a = 0.f, st_e = 0.f;
     int nstep = 0;
-    double b1p = pow((double)b1c, (double)step0), b2p = pow((double)b2c, (double)step0);
+    AdamScalars adam_sc(b1c, b2c, step0);
     float* scr = &S.big.scr[w][0][0];  // tile A: H1, then dZ1
     float* scr2 = &S.act2[w][0][0];     // tile B: H2, then dZ2
 
@@ -399,20 +399,9 @@ PGM_UNROLL_W(PGM_UW_L2)
                         float ls = 0.f;
 #pragma unroll
                         for (int q = 0; q < K; ++q) {
-                            const float V = outv[q], Vp = pv[q], R = pr[q];
-                            float gv;
-                            if (a.hp.use_clipped_value_loss) {
-                                const float dv = V - Vp;
-                                const float vc = Vp + fminf(fmaxf(dv, -clip), clip);
-                                const float l1 = (V - R) * (V - R), l2 = (vc - R) * (vc - R);
-                                const float inr = (dv >= -clip && dv <= clip) ? 1.f : 0.f;
-                                gv = wmax2(l1, l2) * 2.f * (V - R) + wmax2(l2, l1) * 2.f * (vc - R) * inr;
-                                ls += fmaxf(l1, l2);
-                            } else {
-                                gv = 2.f * (V - R);
-                                ls += (R - V) * (R - V);
-                            }
-                            dO[q] = ok ? vscale * gv : 0.f;
+                            const LossTerm vl = value_loss_term(outv[q], pv[q], pr[q], clip, a.hp.use_clipped_value_loss);
+                            ls += vl.loss;
+                            dO[q] = ok ? vscale * vl.grad : 0.f;
                         }
                         if (ok && h == 0) lsum += ls;
                     } else {  // clipped surrogate
@@ -424,6 +413,7 @@ PGM_UNROLL_W(PGM_UW_L2)
                             lp += -0.5f * diff * diff * S.aiv[q] - lstd[q] - LOG_SQRT_2PI;
                         }
                         const float ratio = expf(lp - lpo);
+                        // restates surrogate_term (pgm_ppo_terms.hpp): moving it changes this file's register allocation
                         const float s1 = ratio * ad;
                         const float s2 = fminf(fmaxf(ratio, 1.f - clip), 1.f + clip) * ad;
                         const float inr = (ratio >= 1.f - clip && ratio <= 1.f + clip) ? 1.f : 0.f;
@@ -681,7 +671,8 @@ PGM_UNROLL_W(PGM_UW_L2)
             constexpr int DS = DW + NKT * TS * H * 4;          // byte offset of the new-W1-slice block
             static_assert(NB * 16 * MT == NKT * TS * H, "dW1 exchange block: 16 values per lane and register block");
             static_assert(RS % 4 == 0, "a part's slice is whole 16-B quads");
-            auto spin = [&](const unsigned long long* fl, unsigned want) {  // one lane; bounded
+            // one lane; bounded (restates poll_tagged of pgm_ppo_terms.hpp: moving it changes this file's register allocation)
+            auto spin = [&](const unsigned long long* fl, unsigned want) {
                 unsigned long long x = 0;
                 for (unsigned spins = 0;; ++spins) {
                     x = __hip_atomic_load(fl, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -882,16 +873,10 @@ PGM_UNROLL_W(PGM_UW_L2)
             // ---- Adam: layer 1 first (this part's slice; moments in HBM), its new weights handed to the other
             // parts while the small image (LDS) updates, then the other parts' slices into this part's copy
             ++nstep;
-            b1p *= (double)b1c;
-            b2p *= (double)b2c;
-            const float step_size = (float)(lr / (1.0 - b1p));
-            const float inv_bc2s = 1.f / (float)sqrt(1.0 - b2p);
+            adam_sc.advance(lr, b1c, b2c);
+            const float step_size = adam_sc.step_size, inv_bc2s = adam_sc.inv_bc2s;
             auto adam = [&](float g, float& mm, float& vv, float& pp) {
-                const float gc = g * coef;
-                mm = mm + (1.f - b1c) * (gc - mm);
-                vv = vv * b2c + (1.f - b2c) * (gc * gc);
-                const float den = __builtin_amdgcn_sqrtf(vv) * inv_bc2s + eps;
-                pp -= step_size * mm * __builtin_amdgcn_rcpf(den);
+                adam_step(g, coef, mm, vv, pp, b1c, b2c, step_size, inv_bc2s, eps);
             };
             {
                 // loads of CB blocks in flight at a time (all of them at NS = 4)

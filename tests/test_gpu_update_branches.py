@@ -2,8 +2,11 @@
 
 Eight kernels -- the feature-split kernel (pgm_ppo_fs.hip), the four row-split placements (pgm_ppo_mfma.hip: 16-row
 tiles on four workgroups per tower, MODE 2 / 1 / 0), the VALU kernel (pgm_ppo_update.hip), the wide Humanoid kernel
-(pgm_ppo_wide.hip) and the LayerNorm kernel (pgm_ppo_ln.hip) -- each restate the clipped surrogate, the clipped value
-loss, clip_grad_norm_ and Adam (a2c_ppo_acktr/algo/ppo.py:76-103) and each read pgm_ppo_hparams on their own.  The
+(pgm_ppo_wide.hip) and the LayerNorm kernel (pgm_ppo_ln.hip) -- each read pgm_ppo_hparams on their own and each wire
+the clipped surrogate, the clipped value loss, clip_grad_norm_ and Adam (a2c_ppo_acktr/algo/ppo.py:76-103) into their
+own tiles.  The arithmetic is shared where that left the register-critical kernels' code unchanged
+(pgm_ppo_terms.hpp, tested on the CPU by tests/test_ppo_terms.py) and restated at the sites DESIGN.md 19 lists, so
+every kernel still runs every row.  The
 inputs are tests/branch_inputs.py's: at every Adam step at least 20 % of the rows are clamped to zero gradient (each
 sign case at least 6 %), at least 20 % are outside the clip range but pass, the value clip is active in at least 43 %
 of the elements and each arm of the max wins in at least 8 %; six hyper-parameter rows move every field the kernels read off its default, row c to the side of

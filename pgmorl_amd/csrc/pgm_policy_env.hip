@@ -25,44 +25,35 @@ PGM_STAMP_UNIT(rollout)
 namespace pgm {
 
 // ------------------------------------------------------------------------------------------
-// kernels
+// kernels: each body once, for a Towers type and (where a discrete-action policy can run it) a Head type
+//
+// act: value, action and log-prob of N given rows per task (Policy.act, model.py:57-73)
+template <class Hd>
 struct ActArgs {
     int P, N;
-    Layout L;
     const float* params;
-    const float* obs;
-    const float* noise;
+    const float* obs;  // [P][N][O]
+    const float* rnd;  // [N][width], shared by the tasks; read unless deterministic
     int deterministic;
-    float *value, *action, *logp;
+    float* value;                   // [P][N][K]
+    typename Hd::action_t* action;  // [P][N][width]
+    float* logp;                    // [P][N]
 };
 
-template <int O, int A, int K>
-__global__ __launch_bounds__(RT) void act_forward_kernel(ActArgs a) {
+template <class Tw, class Hd, int O, int A, int K>
+__global__ __launch_bounds__(RT) void act_kernel(ActArgs<Hd> a, typename Tw::Lay L) {
     extern __shared__ __attribute__((aligned(16))) char smem_raw[];
     auto& S = *reinterpret_cast<PolSmem<O, A, K>*>(smem_raw);
-    const int p = blockIdx.x, t = threadIdx.x, N = a.N;
-    const float* prm = a.params + (size_t)p * a.L.total;
-    PolReg<O, A, K> R;
-    load_policy(S, prm, a.L);
-    load_polreg(R, prm, a.L);
-    for (int i = t; i < N * O; i += RT) S.x[i / O][i % O] = a.obs[(size_t)p * N * O + i];
+    const int p = blockIdx.x, N = a.N;
+    constexpr int W = Hd::template width<A>;
+    const float* prm = a.params + (size_t)p * L.total;
+    typename Tw::template Reg<O, A, K> R;
+    load_policy<Tw, Hd::has_logstd>(S, R, prm, L);
+    load_rows(S, a.obs + (size_t)p * N * O, N);
     __syncthreads();
-    policy_forward(S, R, N, prm, a.L);
-    for (int i = t; i < N * K; i += RT) a.value[(size_t)p * N * K + i] = S.val[i / K][i % K];
-    for (int i = t; i < N * A; i += RT) {
-        const int n = i / A, j = i % A;
-        const float mu = S.mu[n][j], ls = S.logstd[j], sd = expf(ls);
-        const float act = a.deterministic ? mu : fmaf(a.noise[i], sd, mu);
-        const float dz = (act - mu) / sd;
-        S.lp[n][j] = -0.5f * dz * dz - ls - LOG_SQRT_2PI;
-        a.action[(size_t)p * N * A + i] = act;
-    }
-    __syncthreads();
-    if (t < N) {
-        float s = 0.f;
-        for (int j = 0; j < A; ++j) s += S.lp[t][j];
-        a.logp[(size_t)p * N + t] = s;
-    }
+    policy_forward<Tw>(S, R, N, prm, L);
+    store_values(S, a.value + (size_t)p * N * K, N);
+    Hd::emit(S, N, a.deterministic ? nullptr : a.rnd, nullptr, a.action + (size_t)p * N * W, a.logp + (size_t)p * N);
 }
 
 struct EnvArgs {
@@ -86,37 +77,15 @@ __global__ __launch_bounds__(RT) void env_kernel(EnvArgs a) {
     load_spec(E, a.spec, a.st.s0, N);
     load_env(E, a.st, a.ns, p, N);
     __syncthreads();
-    if (a.reset) {  // fresh make_vec_envs + reset(): vec_normalize.py:10-27,63-66
-        if (t < N) {
-            E.elapsed[t] = 0;
-            E.ret[t] = 0.0;
-        }
-        if (t == 0) E.obj_valid = 0;
-        const double dn = (double)N;
-        for (int o = t; o < O; o += RT) {
-            double sum = 0.0;
+    if (a.reset) {
+        if (t < N) E.elapsed[t] = 0;
+        for (int o = t; o < O; o += RT)
             for (int n = 0; n < N; ++n) {
                 const double v = sp.s0(n, o);
                 E.snew[n][o] = v;
                 E.s[n][o] = v;
-                sum += v;
             }
-            if (nc.use_ob) {
-                const double bm = sum / dn;
-                double sq = 0.0;
-                for (int n = 0; n < N; ++n) sq += (E.snew[n][o] - bm) * (E.snew[n][o] - bm);
-                chan_merge(E.ob_mean[o], E.ob_var[o], E.ob_count, bm, sq / dn, dn);
-                E.ob_inv[o] = 1.0 / sqrt(E.ob_var[o] + nc.eps);
-            }
-        }
-        __syncthreads();
-        if (t == 0 && nc.use_ob) E.ob_count += dn;
-        for (int i = t; i < N * O; i += RT) {
-            const int o = i % O;
-            double v = E.snew[i / O][o];
-            if (nc.use_ob) v = clipd((v - E.ob_mean[o]) * E.ob_inv[o], -nc.clipob, nc.clipob);
-            a.obs_out[(size_t)p * N * O + i] = (float)v;
-        }
+        vecnorm_reset(E, N, nc, a.obs_out + (size_t)p * N * O);
     } else {
         for (int i = t; i < N * A; i += RT) {
             const int j = i % A;
@@ -133,9 +102,9 @@ __global__ __launch_bounds__(RT) void env_kernel(EnvArgs a) {
     store_env(E, a.st, a.ns, p, N);
 }
 
-
-template <int O, int A, int K>
-__global__ __launch_bounds__(RT) void rollout_kernel(RolloutArgs a) {
+// fused rollout, block form (Gaussian head on the device envs).  L is the towers' layout (a.L for the plain ones).
+template <class Tw, int O, int A, int K>
+__global__ __launch_bounds__(RT) void rollout_kernel(RolloutArgs a, typename Tw::Lay L) {
     extern __shared__ __attribute__((aligned(16))) char smem_raw[];
     auto& S = *reinterpret_cast<StepSmem<O, A, K>*>(smem_raw);
     auto& P = S.pol;
@@ -143,7 +112,7 @@ __global__ __launch_bounds__(RT) void rollout_kernel(RolloutArgs a) {
     const int p = blockIdx.x, t = threadIdx.x, N = a.N, T = a.T;
     const NormCfg nc = norm_cfg(a.ns);
     const Spec<O, A, K> sp{E, a.spec, a.st.s0};
-    const float* prm = a.params + (size_t)p * a.L.total;
+    const float* prm = a.params + (size_t)p * L.total;
     float* obs = a.rb.obs + (size_t)p * (T + 1) * N * O;
     float* act = a.rb.actions + (size_t)p * T * N * A;
     float* logp = a.rb.logp + (size_t)p * T * N;
@@ -152,9 +121,8 @@ __global__ __launch_bounds__(RT) void rollout_kernel(RolloutArgs a) {
     float* masks = a.rb.masks + (size_t)p * (T + 1) * N;
     float* bad = a.rb.bad_masks + (size_t)p * (T + 1) * N;
 
-    PolReg<O, A, K> R;
-    load_policy(P, prm, a.L);
-    load_polreg(R, prm, a.L);
+    typename Tw::template Reg<O, A, K> R;
+    load_policy<Tw, true>(P, R, prm, L);
     load_spec(E, a.spec, a.st.s0, N);
     load_env(E, a.st, a.ns, p, N);
     if (a.carry) {  // after_update(): slot T -> slot 0 (storage.py:71-75); each thread re-reads its own writes
@@ -164,7 +132,7 @@ __global__ __launch_bounds__(RT) void rollout_kernel(RolloutArgs a) {
             bad[t] = bad[(size_t)T * N + t];
         }
     }
-    for (int i = t; i < N * O; i += RT) P.x[i / O][i % O] = obs[i];
+    load_rows(P, obs, N);
     __syncthreads();
 
     // the lane drawing (n, a) of each step keeps its noise one step ahead in a register
@@ -179,9 +147,9 @@ __global__ __launch_bounds__(RT) void rollout_kernel(RolloutArgs a) {
             eps_next = a.noise ? a.noise[idx] : counter_normal(a.seed, idx);
         }
         PGM_STAMP(0);
-        policy_forward(P, R, N, prm, a.L);
+        policy_forward<Tw>(P, R, N, prm, L);
         PGM_STAMP(1);
-        for (int i = t; i < N * K; i += RT) val[(size_t)step * N * K + i] = P.val[i / K][i % K];
+        store_values(P, val + (size_t)step * N * K, N);
         sample_actions(P, E, sp, N, eps, act + (size_t)step * N * A);
         PGM_STAMP(2);
         if (t < N) {
@@ -199,28 +167,28 @@ __global__ __launch_bounds__(RT) void rollout_kernel(RolloutArgs a) {
         PGM_STAMP(5);
     }
     // bootstrap value (mopg.py:132-135) -> value_preds[T] (storage.py:85)
-    policy_forward(P, R, N, prm, a.L);
-    for (int i = t; i < N * K; i += RT) val[(size_t)T * N * K + i] = P.val[i / K][i % K];
+    policy_forward<Tw>(P, R, N, prm, L);
+    store_values(P, val + (size_t)T * N * K, N);
     __syncthreads();
     store_env(E, a.st, a.ns, p, N);
     PGM_STAMP_FLUSH;
 }
 
-template <int O, int A, int K>
-__global__ __launch_bounds__(RT) void eval_kernel(EvalArgs a) {
+// deterministic evaluation, block form (mopg.py:25-46)
+template <class Tw, int O, int A, int K>
+__global__ __launch_bounds__(RT) void eval_kernel(EvalArgs a, typename Tw::Lay L) {
     extern __shared__ __attribute__((aligned(16))) char smem_raw[];
     auto& S = *reinterpret_cast<StepSmem<O, A, K>*>(smem_raw);
     auto& P = S.pol;
     auto& E = S.env;
     const int p = blockIdx.x, t = threadIdx.x;
-    const float* prm = a.params + (size_t)p * a.L.total;
-    PolReg<O, A, K> R;
-    load_policy(P, prm, a.L);
-    load_polreg(R, prm, a.L);
+    const float* prm = a.params + (size_t)p * L.total;
+    typename Tw::template Reg<O, A, K> R;
+    load_policy<Tw, true>(P, R, prm, L);
     load_spec(E, a.spec, a.s0_eval, 1);
-    for (int o = t; o < O; o += RT) {  // mopg.py:37-38: fp64 normalisation with fixed eps/clip
+    for (int o = t; o < O; o += RT) {
         E.ob_mean[o] = a.use_ob ? a.ob_mean[(size_t)p * O + o] : 0.0;
-        E.ob_inv[o] = a.use_ob ? 1.0 / sqrt(a.ob_var[(size_t)p * O + o] + 1e-8) : 1.0;
+        E.ob_inv[o] = a.use_ob ? eval_ob_inv(a.ob_var[(size_t)p * O + o]) : 1.0;
     }
     if (t < K) E.objsum[t] = 0.0;
     __syncthreads();
@@ -232,161 +200,9 @@ __global__ __launch_bounds__(RT) void eval_kernel(EvalArgs a) {
         double g = 1.0;
         __syncthreads();
         while (true) {
-            for (int o = t; o < O; o += RT) {  // obs is NOT rounded through fp32 before normalising
-                double v = E.s[0][o];
-                if (a.use_ob) v = clipd((v - E.ob_mean[o]) * E.ob_inv[o], -10.0, 10.0);
-                P.x[0][o] = (float)v;
-            }
+            for (int o = t; o < O; o += RT) P.x[0][o] = eval_normalise(E.s[0][o], a.use_ob, E.ob_mean[o], E.ob_inv[o]);
             lds_sync();
-            policy_forward(P, R, 1, prm, a.L);
-            if (t < A) E.ac[0][t] = clipd((double)P.mu[0][t], sp.lo(t), sp.hi(t));
-            lds_sync();
-            env_dynamics(E, sp, 1, a.spec.max_episode_steps);
-            if (t < K) E.objsum[t] += g * E.objraw[0][t];
-            if (!a.raw) g *= a.gamma;
-            const int done = E.done[0];
-            for (int o = t; o < O; o += RT) E.s[0][o] = E.snew[0][o];
-            lds_sync();
-            if (done) break;
-        }
-    }
-    if (t < K) a.objs[(size_t)p * K + t] = E.objsum[t] / (double)a.eval_num;
-}
-
-// ------------------------------------------------------------------------------------------
-// LayerNorm towers (pgm_dims.LN = 1): the kernels above with policy_forward_ln (pgm_policy_dev.hpp)
-template <int O, int A, int K>
-__global__ __launch_bounds__(RT) void act_forward_ln_kernel(ActArgs a, LayoutLN L) {
-    extern __shared__ __attribute__((aligned(16))) char smem_raw[];
-    auto& S = *reinterpret_cast<PolSmem<O, A, K>*>(smem_raw);
-    const int p = blockIdx.x, t = threadIdx.x, N = a.N;
-    const float* prm = a.params + (size_t)p * L.total;
-    PolRegLN<O, A, K> R;
-    load_policy_ln(S, prm, L);
-    load_polreg_ln(R, prm, L);
-    for (int i = t; i < N * opad<O>(); i += RT) {  // rows zero-padded to the float4 reads of layer 1
-        const int n = i / opad<O>(), o = i % opad<O>();
-        S.x[n][o] = o < O ? a.obs[((size_t)p * N + n) * O + o] : 0.f;
-    }
-    __syncthreads();
-    policy_forward_ln(S, R, N);
-    for (int i = t; i < N * K; i += RT) a.value[(size_t)p * N * K + i] = S.val[i / K][i % K];
-    for (int i = t; i < N * A; i += RT) {
-        const int n = i / A, j = i % A;
-        const float mu = S.mu[n][j], ls = S.logstd[j], sd = expf(ls);
-        const float act = a.deterministic ? mu : fmaf(a.noise[i], sd, mu);
-        const float dz = (act - mu) / sd;
-        S.lp[n][j] = -0.5f * dz * dz - ls - LOG_SQRT_2PI;
-        a.action[(size_t)p * N * A + i] = act;
-    }
-    __syncthreads();
-    if (t < N) {
-        float s = 0.f;
-        for (int j = 0; j < A; ++j) s += S.lp[t][j];
-        a.logp[(size_t)p * N + t] = s;
-    }
-}
-
-template <int O, int A, int K>
-__global__ __launch_bounds__(RT) void rollout_ln_kernel(RolloutArgs a, LayoutLN L) {
-    extern __shared__ __attribute__((aligned(16))) char smem_raw[];
-    auto& S = *reinterpret_cast<StepSmem<O, A, K>*>(smem_raw);
-    auto& P = S.pol;
-    auto& E = S.env;
-    const int p = blockIdx.x, t = threadIdx.x, N = a.N, T = a.T;
-    const NormCfg nc = norm_cfg(a.ns);
-    const Spec<O, A, K> sp{E, a.spec, a.st.s0};
-    const float* prm = a.params + (size_t)p * L.total;
-    float* obs = a.rb.obs + (size_t)p * (T + 1) * N * O;
-    float* act = a.rb.actions + (size_t)p * T * N * A;
-    float* logp = a.rb.logp + (size_t)p * T * N;
-    float* val = a.rb.values + (size_t)p * (T + 1) * N * K;
-    float* rew = a.rb.rewards + (size_t)p * T * N * K;
-    float* masks = a.rb.masks + (size_t)p * (T + 1) * N;
-    float* bad = a.rb.bad_masks + (size_t)p * (T + 1) * N;
-
-    PolRegLN<O, A, K> R;
-    load_policy_ln(P, prm, L);
-    load_polreg_ln(R, prm, L);
-    load_spec(E, a.spec, a.st.s0, N);
-    load_env(E, a.st, a.ns, p, N);
-    if (a.carry) {  // after_update(): slot T -> slot 0 (storage.py:71-75); each thread re-reads its own writes
-        for (int i = t; i < N * O; i += RT) obs[i] = obs[(size_t)T * N * O + i];
-        if (t < N) {
-            masks[t] = masks[(size_t)T * N + t];
-            bad[t] = bad[(size_t)T * N + t];
-        }
-    }
-    for (int i = t; i < NMAX * opad<O>(); i += RT) (&P.x[0][0])[i] = 0.f;  // the float4 pad columns stay zero
-    __syncthreads();
-    for (int i = t; i < N * O; i += RT) P.x[i / O][i % O] = obs[i];
-    __syncthreads();
-
-    // the lane drawing (n, a) of each step keeps its noise one step ahead in a register
-    const bool drawer = t < N * A;
-    float eps_next = 0.f;
-    if (drawer) eps_next = a.noise ? a.noise[t] : counter_normal(a.seed, (uint64_t)t);
-    for (int step = 0; step < T; ++step) {
-        const float eps = eps_next;
-        if (drawer && step + 1 < T) {
-            const size_t idx = (size_t)(step + 1) * N * A + t;
-            eps_next = a.noise ? a.noise[idx] : counter_normal(a.seed, idx);
-        }
-        policy_forward_ln(P, R, N);
-        for (int i = t; i < N * K; i += RT) val[(size_t)step * N * K + i] = P.val[i / K][i % K];
-        sample_actions(P, E, sp, N, eps, act + (size_t)step * N * A);
-        if (t < N) {
-            float s = 0.f;
-            for (int j = 0; j < A; ++j) s += P.lp[t][j];
-            logp[(size_t)step * N + t] = s;
-        }
-        env_dynamics(E, sp, N, a.spec.max_episode_steps);
-        vecnorm_stats(E, sp, N, nc);
-        vecnorm_emit<O, A, K, opad<O>()>(E, N, nc, P.x, obs + (size_t)(step + 1) * N * O,
-                                         rew + (size_t)step * N * K, masks + (size_t)(step + 1) * N,
-                                         bad + (size_t)(step + 1) * N);
-    }
-    // bootstrap value (mopg.py:132-135) -> value_preds[T] (storage.py:85)
-    policy_forward_ln(P, R, N);
-    for (int i = t; i < N * K; i += RT) val[(size_t)T * N * K + i] = P.val[i / K][i % K];
-    __syncthreads();
-    store_env(E, a.st, a.ns, p, N);
-}
-
-template <int O, int A, int K>
-__global__ __launch_bounds__(RT) void eval_ln_kernel(EvalArgs a, LayoutLN L) {
-    extern __shared__ __attribute__((aligned(16))) char smem_raw[];
-    auto& S = *reinterpret_cast<StepSmem<O, A, K>*>(smem_raw);
-    auto& P = S.pol;
-    auto& E = S.env;
-    const int p = blockIdx.x, t = threadIdx.x;
-    const float* prm = a.params + (size_t)p * L.total;
-    PolRegLN<O, A, K> R;
-    load_policy_ln(P, prm, L);
-    load_polreg_ln(R, prm, L);
-    load_spec(E, a.spec, a.s0_eval, 1);
-    for (int o = t; o < O; o += RT) {  // mopg.py:37-38: fp64 normalisation with fixed eps/clip
-        E.ob_mean[o] = a.use_ob ? a.ob_mean[(size_t)p * O + o] : 0.0;
-        E.ob_inv[o] = a.use_ob ? 1.0 / sqrt(a.ob_var[(size_t)p * O + o] + 1e-8) : 1.0;
-    }
-    if (t < opad<O>()) P.x[0][t] = 0.f;
-    if (t < K) E.objsum[t] = 0.0;
-    __syncthreads();
-    for (int e = 0; e < a.eval_num; ++e) {
-        const double* s0 = a.s0_eval + (size_t)e * O;
-        const Spec<O, A, K> sp{E, a.spec, s0};
-        for (int o = t; o < O; o += RT) E.s[0][o] = s0[o];
-        if (t == 0) E.elapsed[0] = 0;
-        double g = 1.0;
-        __syncthreads();
-        while (true) {
-            for (int o = t; o < O; o += RT) {  // obs is NOT rounded through fp32 before normalising
-                double v = E.s[0][o];
-                if (a.use_ob) v = clipd((v - E.ob_mean[o]) * E.ob_inv[o], -10.0, 10.0);
-                P.x[0][o] = (float)v;
-            }
-            lds_sync();
-            policy_forward_ln(P, R, 1);
+            policy_forward<Tw>(P, R, 1, prm, L);
             if (t < A) E.ac[0][t] = clipd((double)P.mu[0][t], sp.lo(t), sp.hi(t));
             lds_sync();
             env_dynamics(E, sp, 1, a.spec.max_episode_steps);
@@ -415,19 +231,30 @@ int pgm_act_forward(const pgm_dims* d, const float* params, const float* obs, co
         set_error("pgm_act_forward: null pointer (noise is required unless deterministic)");
         return PGM_E_INVALID_ARG;
     }
-    ActArgs a{d->P, d->N, make_layout(d->O, d->A, d->K, d->H), params, obs, noise, deterministic, value, action, logp};
-    if (d->LN) {
-        const LayoutLN LL = make_layout_ln(d->O, d->A, d->K, d->H);
-        return dispatch_dims_ln(d, "pgm_act_forward", [&](auto o, auto aa, auto k) {
-            constexpr int O = decltype(o)::value, A = decltype(aa)::value, K = decltype(k)::value;
-            return launch_smem_ln(act_forward_ln_kernel<O, A, K>, d->P, sizeof(PolSmem<O, A, K>), (hipStream_t)stream,
-                                  "pgm_act_forward", a, LL);
-        });
-    }
-    return dispatch_dims(d->O, d->A, d->K, "pgm_act_forward", [&](auto o, auto aa, auto k) {
+    ActArgs<GaussHead> a{d->P, d->N, params, obs, noise, deterministic, value, action, logp};
+    return dispatch_towers(d, "pgm_act_forward", [&](auto tw, const auto& L, auto o, auto aa, auto k) {
         constexpr int O = decltype(o)::value, A = decltype(aa)::value, K = decltype(k)::value;
-        return launch_smem(act_forward_kernel<O, A, K>, d->P, sizeof(PolSmem<O, A, K>), (hipStream_t)stream, a,
-                           "pgm_act_forward");
+        return launch_smem(act_kernel<decltype(tw), GaussHead, O, A, K>, d->P, sizeof(PolSmem<O, A, K>),
+                           (hipStream_t)stream, "pgm_act_forward", a, L);
+    });
+}
+
+// Discrete-action policies.  Arguments are validated before any device work: NULL pointers, check_dims, the dim set,
+// LN.
+int pgm_act_forward_cat(const pgm_dims* d, const float* params, const float* obs, const float* uniforms,
+                        int32_t deterministic, float* value, int32_t* action, float* logp, pgm_stream_t stream) {
+    if (!d || !params || !obs || !value || !action || !logp || (!deterministic && !uniforms)) {
+        set_error("pgm_act_forward_cat: null pointer (uniforms is required unless deterministic)");
+        return PGM_E_INVALID_ARG;
+    }
+    if (int rc = check_dims(d, "pgm_act_forward_cat")) return rc;
+    if (int rc = check_cat_dims(d, "pgm_act_forward_cat")) return rc;
+    if (int rc = check_cat_ln(d, "pgm_act_forward_cat")) return rc;
+    ActArgs<CatHead> a{d->P, d->N, params, obs, uniforms, deterministic, value, action, logp};
+    return dispatch_towers_cat(d, "pgm_act_forward_cat", [&](auto tw, const auto& L, auto o, auto aa, auto k) {
+        constexpr int O = decltype(o)::value, A = decltype(aa)::value, K = decltype(k)::value;
+        return launch_smem(act_kernel<decltype(tw), CatHead, O, A, K>, d->P, sizeof(PolSmem<O, A, K>),
+                           (hipStream_t)stream, "pgm_act_forward_cat", a, L);
     });
 }
 
@@ -441,6 +268,13 @@ static int env_common(const pgm_dims* d, const pgm_env_spec* spec, const pgm_env
     return PGM_OK;
 }
 
+static int launch_env(const pgm_dims* d, const EnvArgs& a, pgm_stream_t stream, const char* what) {
+    return dispatch_dims(d->O, d->A, d->K, what, [&](auto o, auto aa, auto k) {
+        constexpr int O = decltype(o)::value, A = decltype(aa)::value, K = decltype(k)::value;
+        return launch_smem(env_kernel<O, A, K>, d->P, sizeof(StepSmem<O, A, K>), (hipStream_t)stream, what, a);
+    });
+}
+
 int pgm_env_reset(const pgm_dims* d, const pgm_env_spec* spec, const pgm_env_state* st,
                   const pgm_norm_state* ns, float* obs_out, pgm_stream_t stream) {
     if (int rc = env_common(d, spec, st, ns, "pgm_env_reset")) return rc;
@@ -448,12 +282,8 @@ int pgm_env_reset(const pgm_dims* d, const pgm_env_spec* spec, const pgm_env_sta
         set_error("pgm_env_reset: null obs_out");
         return PGM_E_INVALID_ARG;
     }
-    EnvArgs a{d->P, d->N, *spec, *st, *ns, nullptr, obs_out, nullptr, nullptr, nullptr, 1};
-    return dispatch_dims(d->O, d->A, d->K, "pgm_env_reset", [&](auto o, auto aa, auto k) {
-        constexpr int O = decltype(o)::value, A = decltype(aa)::value, K = decltype(k)::value;
-        return launch_smem(env_kernel<O, A, K>, d->P, sizeof(StepSmem<O, A, K>), (hipStream_t)stream, a,
-                           "pgm_env_reset");
-    });
+    return launch_env(d, EnvArgs{d->P, d->N, *spec, *st, *ns, nullptr, obs_out, nullptr, nullptr, nullptr, 1}, stream,
+                      "pgm_env_reset");
 }
 
 int pgm_env_step(const pgm_dims* d, const pgm_env_spec* spec, const pgm_env_state* st,
@@ -464,12 +294,8 @@ int pgm_env_step(const pgm_dims* d, const pgm_env_spec* spec, const pgm_env_stat
         set_error("pgm_env_step: null pointer");
         return PGM_E_INVALID_ARG;
     }
-    EnvArgs a{d->P, d->N, *spec, *st, *ns, action, obs_out, reward_out, masks_out, bad_masks_out, 0};
-    return dispatch_dims(d->O, d->A, d->K, "pgm_env_step", [&](auto o, auto aa, auto k) {
-        constexpr int O = decltype(o)::value, A = decltype(aa)::value, K = decltype(k)::value;
-        return launch_smem(env_kernel<O, A, K>, d->P, sizeof(StepSmem<O, A, K>), (hipStream_t)stream, a,
-                           "pgm_env_step");
-    });
+    return launch_env(d, EnvArgs{d->P, d->N, *spec, *st, *ns, action, obs_out, reward_out, masks_out, bad_masks_out, 0},
+                      stream, "pgm_env_step");
 }
 
 int pgm_rollout(const pgm_dims* d, const float* params, const pgm_env_spec* spec, const pgm_env_state* st,
@@ -490,21 +316,15 @@ int pgm_rollout(const pgm_dims* d, const float* params, const pgm_env_spec* spec
     }
     RolloutArgs a{d->P, d->N, d->T, make_layout(d->O, d->A, d->K, d->H), params, *spec, *st, *ns, *rb,
                   noise, seed, carry};
-    if (d->LN) {  // LayerNorm towers: one kernel family, opts ignored
-        const LayoutLN LL = make_layout_ln(d->O, d->A, d->K, d->H);
-        return dispatch_dims_ln(d, "pgm_rollout", [&](auto o, auto aa, auto k) {
-            constexpr int O = decltype(o)::value, A = decltype(aa)::value, K = decltype(k)::value;
-            return launch_smem_ln(rollout_ln_kernel<O, A, K>, d->P, sizeof(StepSmem<O, A, K>), (hipStream_t)stream,
-                                  "pgm_rollout", a, LL);
-        });
+    // LayerNorm towers: one kernel family, opts ignored; plain: the block kernel on request (A/B, tests) or last
+    if (!d->LN && o.rollout_kernel != 1) {
+        if (rollout_lanes_supported(d)) return launch_rollout_lanes(d, a, (hipStream_t)stream);
+        if (rollout_wide_supported(d)) return launch_rollout_wide(d, a, (hipStream_t)stream);
     }
-    const bool block = o.rollout_kernel == 1;  // the workgroup-per-step kernel (A/B, tests)
-    if (!block && rollout_lanes_supported(d)) return launch_rollout_lanes(d, a, (hipStream_t)stream);
-    if (!block && rollout_wide_supported(d)) return launch_rollout_wide(d, a, (hipStream_t)stream);
-    return dispatch_dims(d->O, d->A, d->K, "pgm_rollout", [&](auto o, auto aa, auto k) {
+    return dispatch_towers(d, "pgm_rollout", [&](auto tw, const auto& L, auto o, auto aa, auto k) {
         constexpr int O = decltype(o)::value, A = decltype(aa)::value, K = decltype(k)::value;
-        return launch_smem(rollout_kernel<O, A, K>, d->P, sizeof(StepSmem<O, A, K>), (hipStream_t)stream, a,
-                           "pgm_rollout");
+        return launch_smem(rollout_kernel<decltype(tw), O, A, K>, d->P, sizeof(StepSmem<O, A, K>), (hipStream_t)stream,
+                           "pgm_rollout", a, L);
     });
 }
 
@@ -521,21 +341,15 @@ int pgm_eval(const pgm_dims* d, const float* params, const pgm_env_spec* spec, c
     }
     EvalArgs a{d->P, make_layout(d->O, d->A, d->K, d->H), params, *spec, ob_mean, ob_var, s0_eval,
                eval_num, use_ob_rms, raw, gamma, objs_out};
-    if (d->LN) {  // LayerNorm towers: one kernel family, opts ignored
-        const LayoutLN LL = make_layout_ln(d->O, d->A, d->K, d->H);
-        return dispatch_dims_ln(d, "pgm_eval", [&](auto o, auto aa, auto k) {
-            constexpr int O = decltype(o)::value, A = decltype(aa)::value, K = decltype(k)::value;
-            return launch_smem_ln(eval_ln_kernel<O, A, K>, d->P, sizeof(StepSmem<O, A, K>), (hipStream_t)stream,
-                                  "pgm_eval", a, LL);
-        });
+    // LayerNorm towers: one kernel family, opts ignored; plain: the block kernel on request (A/B, tests) or last
+    if (!d->LN && o.eval_kernel != 1) {
+        if (eval_waves_supported(d, eval_num)) return launch_eval_waves(d, a, (hipStream_t)stream);
+        if (eval_wide_supported(d, eval_num)) return launch_eval_wide(d, a, (hipStream_t)stream);
     }
-    const bool block = o.eval_kernel == 1;  // the workgroup-per-step kernel (A/B, tests)
-    if (!block && eval_waves_supported(d, eval_num)) return launch_eval_waves(d, a, (hipStream_t)stream);
-    if (!block && eval_wide_supported(d, eval_num)) return launch_eval_wide(d, a, (hipStream_t)stream);
-    return dispatch_dims(d->O, d->A, d->K, "pgm_eval", [&](auto o, auto aa, auto k) {
+    return dispatch_towers(d, "pgm_eval", [&](auto tw, const auto& L, auto o, auto aa, auto k) {
         constexpr int O = decltype(o)::value, A = decltype(aa)::value, K = decltype(k)::value;
-        return launch_smem(eval_kernel<O, A, K>, d->P, sizeof(StepSmem<O, A, K>), (hipStream_t)stream, a,
-                           "pgm_eval");
+        return launch_smem(eval_kernel<decltype(tw), O, A, K>, d->P, sizeof(StepSmem<O, A, K>), (hipStream_t)stream,
+                           "pgm_eval", a, L);
     });
 }
 }  // extern "C"

@@ -264,10 +264,12 @@ __host__ __device__ __forceinline__ uint64_t splitmix64(uint64_t x) {
     x = (x ^ (x >> 27)) * 0x94D049BB133111EBull;
     return x ^ (x >> 31);
 }
-// standard normal for element i of stream `seed` (Box-Muller on one 64-bit hash)
+// standard normal for element i of stream `seed` (Box-Muller on one 64-bit hash); oracle/streams.py restates it.
+// u1: the fp32 sum rounds the half away once the 24 bits reach 2^23 (ties to even), so the top value gives exactly 1
+// (z = 0); it never gives 0, so logf stays finite and |z| <= sqrt(-2 ln 2^-25).
 __device__ __forceinline__ float counter_normal(uint64_t seed, uint64_t i) {
     uint64_t h = splitmix64(splitmix64(seed * 0xD1B54A32D192ED03ull + 0x632BE59BD9B4E019ull) ^ i);
-    float u1 = ((uint32_t)(h >> 40) + 0.5f) * (1.0f / 16777216.0f);          // (0,1)
+    float u1 = ((uint32_t)(h >> 40) + 0.5f) * (1.0f / 16777216.0f);          // (0,1]
     float u2 = (uint32_t)(h & 0xFFFFFFu) * (1.0f / 16777216.0f);             // [0,1)
     return sqrtf(-2.0f * logf(u1)) * cospif(2.0f * u2);
 }

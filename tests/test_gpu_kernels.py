@@ -109,8 +109,13 @@ def test_gae(gpu, use_gae, proper, N, K, T):
     rew, val, masks, bad = _random_storage(P, T, N, K, seed=T + N)
     for dst, src in ((tb.rewards, rew), (tb.values, val), (tb.masks, masks), (tb.bad_masks, bad)):
         dst.copy_(torch.from_numpy(src))
+    tb.returns.fill_(-777.0)
     tb.gae()
     got = tb.returns.cpu().numpy()
+    if use_gae:  # returns[T]: left alone under GAE, next_value otherwise (storage.py:83-100)
+        assert (got[:, T] == -777.0).all()
+    else:
+        np.testing.assert_array_equal(got[:, T], val[:, T])
     for p in range(P):
         r, v = torch.from_numpy(rew[p]).double(), torch.from_numpy(val[p]).double()
         m = torch.from_numpy(masks[p]).double().unsqueeze(-1)

@@ -42,7 +42,11 @@
  *   pgm_ppo_update_cat    PPO.update epochs x minibatches with FixedCategorical log_probs / entropy
  *                                                           a2c_ppo_acktr/algo/ppo.py:58-115, model.py:75-82
  *   pgm_uniform_noise     Categorical.sample's multinomial draw  (perf-mode RNG replacement)
- *   pgm_randperm          SubsetRandomSampler's randperm     (perf-mode RNG replacement)
+ *   pgm_rollout_dst       the rollout loop on the device Deep Sea Treasure   morl/mopg.py:103-135,
+ *                                                           environments/deep_sea_treasure.py:111-183
+ *   pgm_eval_dst          evaluation() on the device Deep Sea Treasure       morl/mopg.py:25-46
+ *   pgm_dst_transition    the Deep Sea Treasure step on the host   environments/deep_sea_treasure.py:111-183
+ *   pgm_randperm         SubsetRandomSampler's randperm     (perf-mode RNG replacement)
  *   pgm_normal_noise      Normal.sample's torch.normal draw  (perf-mode RNG replacement)
  *
  * Layouts (row-major, fp32 unless noted; P = tasks, N = envs per task, T = rollout steps,
@@ -125,6 +129,7 @@ extern "C" {
 
 /* pgm_abi_features() bits: additions that leave PGM_ABI_VERSION / PGM_ABI_MINOR alone are discovered here. */
 #define PGM_FEATURE_CATEGORICAL 1 /* the *_cat entry points, pgm_param_layout_cat, pgm_uniform_noise */
+#define PGM_FEATURE_DST_DEVICE 2  /* pgm_rollout_dst, pgm_eval_dst, pgm_dst_transition: Deep Sea Treasure on the device */
 
 typedef void* pgm_stream_t; /* a hipStream_t (0 = the null stream) */
 
@@ -352,7 +357,8 @@ int pgm_normal_noise(int64_t n, uint64_t seed, float* out, pgm_stream_t stream);
 /* ---- Discrete-action policies (pgm_abi_features() & PGM_FEATURE_CATEGORICAL).  The policy head is the reference's
  * Categorical (model.py:33-35, distributions.py:54-68): logits z = Linear(actor features), one integer action per
  * step.  In these entry points pgm_dims.A is the NUMBER OF ACTIONS; the stored action has width 1.  Environments are
- * host-stepped (pgm_env_ingest accepts the categorical dim sets; it never reads the action).  Built for
+ * host-stepped (pgm_env_ingest accepts the categorical dim sets; it never reads the action) or, for Deep Sea Treasure,
+ * stepped on the device inside the fused rollout (pgm_rollout_dst / pgm_eval_dst below).  Built for
  * (O, A, K) = (3, 4, 2) (Deep Sea Treasure); pgm_dims.LN must be 0 (LayerNorm towers with a Categorical head are not
  * built: PGM_E_UNSUPPORTED).  Every entry point validates before any device work: NULL pointers, check of the dims,
  * the dim set, the step index or E, LN.
@@ -407,6 +413,51 @@ size_t pgm_ppo_update_cat_workspace_bytes(const pgm_dims* d); /* monotone in d->
 /* n uniform fp32 draws in [0, 1) with 24 random bits into out, element i keyed by (seed, i) through the counter hash
  * of pgm_normal_noise: the perf-mode stream of the sampling rule. */
 int pgm_uniform_noise(int64_t n, uint64_t seed, float* out, pgm_stream_t stream);
+
+/* ---- Deep Sea Treasure on the device (pgm_abi_features() & PGM_FEATURE_DST_DEVICE).  The env of the reference's
+ * environments/deep_sea_treasure.py:111-183 as pgmorl_amd/hostenv.py states it: an 11 x 11 grid, cell (r, c) open if
+ * r == 0 or r <= c or a treasure ((1,0) = 1, (2,1) = 3, (4,3) = 8, (7,6) = 20); actions 0 up, 1 down, 2 left, 3 right
+ * (a move off the grid or into a wall stays); step += 1 per transition; on a treasure reward = obj0 = its value and
+ * obj1 = 10 / (step + 1), else 0; done = found || step >= max_steps; bad = time_limit_is_bad && limit && !found; a
+ * done env resets to (0, 0, 0) and the returned observation is the reset one; raw observation
+ * [r / 10, c / 10, step / max_steps], each rounded to fp32 and widened.  The rule is ONE inline function
+ * (pgmorl_amd/csrc/pgm_dst.hpp) used by the two kernels and by pgm_dst_transition.  Dims (3, 4, 2), LN = 0.
+ * Validation before any device work: NULL pointers (PGM_E_INVALID_ARG), the dims, the dim set (PGM_E_UNSUPPORTED), LN,
+ * T <= 0 (PGM_E_SHAPE), eval_num outside 1..8 (PGM_E_INVALID_ARG), max_steps <= 0 (PGM_E_INVALID_ARG). */
+typedef struct pgm_dst_spec {
+    int32_t max_steps;         /* episode step limit (the env's default: 50) */
+    int32_t time_limit_is_bad; /* 0: the limit ends an episode as a termination (the env's own report); 1: as a
+                                  time-limit end (bad_transition, a2c_ppo_acktr/envs.py:122-131) */
+} pgm_dst_spec;
+
+/* T rollout steps of every task in one launch (morl/mopg.py:103-135 with the env, DummyVecEnv's auto-reset
+ * dummy_vec_env.py:45-56 and VecNormalize.step_wait vec_normalize.py:29-43 on the device): per step Policy.act on
+ * rb->obs[p][t] by the sampling rule, the transition of every env, the running statistics (the scalar treasure reward
+ * feeds VecNormalize.ret / ret_rms), insert into slot t + 1; then the bootstrap value into rb->values[p][T].  Writes
+ * what T pgm_rollout_act_cat / pgm_env_ingest pairs plus pgm_rollout_act_cat(T) write, bit for bit.  st->s [P][N][3]
+ * holds (row, col, step) as integer-valued fp64; st->elapsed and st->s0 are not read and may be NULL.  uniforms
+ * [T][N] shared by the tasks, or NULL: element (t, n) is then element t * N + n of pgm_uniform_noise's stream of
+ * `seed`, drawn in the kernel.  carry != 0: slot T -> slot 0 first (storage.py:71-75).  rb->returns / adv are not
+ * touched.  A fresh run starts from st->s = 0 and pgm_env_ingest(t = -1) on the all-zero reset observation. */
+int pgm_rollout_dst(const pgm_dims* d, const float* params, const pgm_dst_spec* env, const pgm_env_state* st,
+                    const pgm_norm_state* ns, const pgm_rollout_buf* rb, const float* uniforms, uint64_t seed,
+                    int32_t carry, pgm_stream_t stream);
+
+/* evaluation() (morl/mopg.py:25-46): eval_num (1..8) episodes per task from (0, 0, 0) with the deterministic action
+ * (the lowest index among the maxima of the logits) on the raw fp64 observation normalised with the frozen ob_mean /
+ * ob_var [P][3] (use_ob_rms; not rounded through fp32 first); per episode acc += disc * obj, disc *= gamma unless raw;
+ * objs_out [P][2] fp64 = sum over episodes / eval_num.  pgm_dims.N and T are ignored. */
+int pgm_eval_dst(const pgm_dims* d, const float* params, const pgm_dst_spec* env, const double* ob_mean,
+                 const double* ob_var, int32_t eval_num, int32_t use_ob_rms, int32_t raw, double gamma,
+                 double* objs_out, pgm_stream_t stream);
+
+/* The env rule on n (state, action) pairs, on the HOST (environments/deep_sea_treasure.py:111-183): launches nothing,
+ * needs no device, every pointer a host pointer.  Outputs: the state after the auto-reset, raw_obs_out [n][3] of that
+ * state, obj_out [n][2], reward_out [n], done_out / bad_out [n]. */
+int pgm_dst_transition(const pgm_dst_spec* spec, int32_t n, const int32_t* row, const int32_t* col,
+                       const int32_t* step, const int32_t* action, int32_t* row_out, int32_t* col_out,
+                       int32_t* step_out, double* raw_obs_out, double* obj_out, double* reward_out, int32_t* done_out,
+                       int32_t* bad_out);
 
 #ifdef __cplusplus
 }

@@ -63,6 +63,11 @@ class PPOHParams(C.Structure):
                 ('num_mini_batch', I32), ('use_clipped_value_loss', I32), ('_pad2', I32)]
 
 
+class DstSpec(C.Structure):
+    """pgm_dst_spec: the device Deep Sea Treasure's step limit and how the limit is reported."""
+    _fields_ = [('max_steps', I32), ('time_limit_is_bad', I32)]
+
+
 class LaunchOpts(C.Structure):
     """pgm_launch_opts (pgm_abi.h): which kernel family an entry point may launch; all zero = automatic."""
     _fields_ = [(n, I32) for n in ('update_kernel', 'update_split', 'fs_one_per_cu', 'rollout_kernel', 'eval_kernel',
@@ -130,14 +135,21 @@ _SIGS = {
                                      C.POINTER(RolloutBuf), P_, P_, P_]),
     'pgm_ppo_update_cat_workspace_bytes': (C.c_size_t, [C.POINTER(Dims)]),
     'pgm_uniform_noise': (C.c_int, [C.c_int64, C.c_uint64, P_, P_]),
+    # Deep Sea Treasure on the device (pgm_abi_features() & FEATURE_DST_DEVICE)
+    'pgm_rollout_dst': (C.c_int, [C.POINTER(Dims), P_, C.POINTER(DstSpec), C.POINTER(EnvState), C.POINTER(NormState),
+                                  C.POINTER(RolloutBuf), P_, C.c_uint64, I32, P_]),
+    'pgm_eval_dst': (C.c_int, [C.POINTER(Dims), P_, C.POINTER(DstSpec), P_, P_, I32, I32, I32, F64, P_, P_]),
+    'pgm_dst_transition': (C.c_int, [C.POINTER(DstSpec), I32] + [P_] * 12),
 }
 # the symbols a library of the same ABI version and minor may lack: discovered through pgm_abi_features
 FEATURE_CATEGORICAL = 1
+FEATURE_DST_DEVICE = 2
 _FEATURE_SYMBOLS = {'pgm_abi_features': 0, 'pgm_param_layout_cat': FEATURE_CATEGORICAL,
                     'pgm_act_forward_cat': FEATURE_CATEGORICAL, 'pgm_rollout_act_cat': FEATURE_CATEGORICAL,
                     'pgm_eval_act_cat': FEATURE_CATEGORICAL, 'pgm_ppo_update_cat': FEATURE_CATEGORICAL,
                     'pgm_ppo_update_cat_workspace_bytes': FEATURE_CATEGORICAL,
-                    'pgm_uniform_noise': FEATURE_CATEGORICAL}
+                    'pgm_uniform_noise': FEATURE_CATEGORICAL, 'pgm_rollout_dst': FEATURE_DST_DEVICE,
+                    'pgm_eval_dst': FEATURE_DST_DEVICE, 'pgm_dst_transition': FEATURE_DST_DEVICE}
 
 EXPORTS = tuple(_SIGS)
 
@@ -206,6 +218,12 @@ def features():
 def require_categorical():
     if not features() & FEATURE_CATEGORICAL:
         raise PGMError('this libpgm.so has no Categorical-head entry points (pgm_abi_features() & 1 is clear); '
+                       'rebuild it with `python -m pgmorl_amd.build`')
+
+
+def require_dst_device():
+    if not features() & FEATURE_DST_DEVICE:
+        raise PGMError('this libpgm.so has no device Deep Sea Treasure entry points (pgm_abi_features() & 2 is clear); '
                        'rebuild it with `python -m pgmorl_amd.build`')
 
 

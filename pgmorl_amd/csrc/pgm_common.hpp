@@ -273,6 +273,11 @@ __device__ __forceinline__ float counter_normal(uint64_t seed, uint64_t i) {
     float u2 = (uint32_t)(h & 0xFFFFFFu) * (1.0f / 16777216.0f);             // [0,1)
     return sqrtf(-2.0f * logf(u1)) * cospif(2.0f * u2);
 }
+// fp32 uniform in [0, 1) with 24 random bits for element i of stream `seed`: the hash of counter_normal
+__device__ __forceinline__ float counter_uniform(uint64_t seed, uint64_t i) {
+    const uint64_t h = splitmix64(splitmix64(seed * 0xD1B54A32D192ED03ull + 0x632BE59BD9B4E019ull) ^ i);
+    return (float)(uint32_t)(h >> 40) * (1.0f / 16777216.0f);
+}
 
 }  // namespace pgm
 

@@ -122,12 +122,7 @@ __global__ __launch_bounds__(RT) void env_ingest_kernel(IngestArgs a) {
     store_env<false>(E, a.st, a.ns, p, N);
 }
 
-// fp32 uniform in [0, 1) with 24 random bits for element i of stream `seed`: the hash of counter_normal
-__device__ __forceinline__ float counter_uniform(uint64_t seed, uint64_t i) {
-    const uint64_t h = splitmix64(splitmix64(seed * 0xD1B54A32D192ED03ull + 0x632BE59BD9B4E019ull) ^ i);
-    return (float)(uint32_t)(h >> 40) * (1.0f / 16777216.0f);
-}
-
+// element i of the perf-mode uniform stream (counter_uniform, pgm_common.hpp: shared with the fused DST rollout)
 __global__ void uniform_kernel(int64_t n, uint64_t seed, float* out) {
     for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x)
         out[i] = counter_uniform(seed, (uint64_t)i);

@@ -60,8 +60,9 @@ def env_names():
 
 
 # Discrete-action envs: env id -> (obs_dim, number of actions, obj_num, max_episode_steps).  They have no SynthMO
-# stand-in and no device env: they are host-stepped (hostenv.DeepSeaTreasureHostVecEnv) and their policies carry the
-# reference's Categorical head (a2c_ppo_acktr/model.py:33-35).
+# stand-in: they are host-stepped (hostenv.DeepSeaTreasureHostVecEnv) or, Deep Sea Treasure with device_env=True,
+# stepped inside the fused kernels of csrc/pgm_dst.hip; their policies carry the reference's Categorical head
+# (a2c_ppo_acktr/model.py:33-35).
 _DISCRETE_ENVS = {
     'MO-DeepSeaTreasure-v0': (3, 4, 2, 50),
 }

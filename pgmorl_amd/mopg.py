@@ -48,11 +48,12 @@ def linear_lr(j, total_num_updates, lr, ratio=1.0):
 
 
 class MOPGPopulation:
-    def __init__(self, args, device='cuda', rng='device', host_env=None):
+    def __init__(self, args, device='cuda', rng='device', host_env=None, device_env=None):
         """host_env (default ``args.host_env``, the --host-env flag; None = the device envs): 'synth',
         'module:callable' or a factory (env_name, P, N, seed) -> hostenv.HostVecEnv.  The environments then run on
         the host and every TaskBatch of this runtime is built over a HostVecEnv of its own task slots (a rank holds
-        host envs for its block of the population only)."""
+        host envs for its block of the population only).  device_env (default ``args.device_env``, the --device-env
+        flag): a discrete-action env runs on the device (TaskBatch(device_env=True)); a no-op on the SynthMO envs."""
         self.args = args
         self.device = torch.device(device)
         self.rng = rng
@@ -62,6 +63,7 @@ class MOPGPopulation:
             from .hostenv import resolve
             host_env = resolve(host_env)
         self.host_env_factory = host_env
+        self.device_env = bool(getattr(args, 'device_env', False) if device_env is None else device_env)
         self.moved_bytes = 0  # snapshot bytes this rank contributed to move_rows (multi-GPU)
 
     @property
@@ -95,7 +97,8 @@ class MOPGPopulation:
                                 obj_rms=a.obj_rms, raw=a.raw, clip_param=a.clip_param, ppo_epoch=a.ppo_epoch,
                                 num_mini_batch=a.num_mini_batch, value_loss_coef=a.value_loss_coef,
                                 entropy_coef=a.entropy_coef, max_grad_norm=a.max_grad_norm, device=self.device,
-                                capacity=cap, layernorm=bool(getattr(a, 'layernorm', False)), host_env=he)
+                                capacity=cap, layernorm=bool(getattr(a, 'layernorm', False)), host_env=he,
+                                device_env=self.device_env)
         else:
             self.tb.set_active(P)
         return self.tb

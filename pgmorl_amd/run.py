@@ -3,7 +3,8 @@
     python -m pgmorl_amd.run --env-name MO-Walker2d-v2 --num-env-steps 5000000 ... [--selection-method ra]
 
 Adds ``--rng {device,host}`` (device counter streams, or the reference's own torch draws for
-bit-compatible runs), ``--device`` and ``--host-env SPEC`` (environments stepped on the host, hostenv.py).
+bit-compatible runs), ``--device``, ``--host-env SPEC`` (environments stepped on the host, hostenv.py) and
+``--device-env`` (a discrete-action env, Deep Sea Treasure, stepped on the device instead).
 """
 import argparse
 import os
@@ -64,6 +65,9 @@ def get_parser():
         help='step the environments on the host (policy, VecNormalize, storage and PPO stay on the device): '
              '"synth" (SynthMO in numpy) or "module:callable" with callable(env_name, seed, rank) -> a gym-style '
              'multi-objective env; default: the device envs')
+    add('--device-env', action='store_true', default=False,
+        help='run a discrete-action env on the device (MO-DeepSeaTreasure-v0: the fused Categorical rollout and '
+             'evaluation) instead of --host-env; no effect on the SynthMO envs, which are device envs already')
     return ap
 
 
@@ -107,11 +111,16 @@ def main(argv=None):
                            f'are built for obs_dim <= {LN_MAX_OBS}; obs_dim {obs_dim} would need a streamed layer-1 '
                            f'LayerNorm kernel, which does not exist')
     from .envspec import discrete_env_names
-    if args.env_name in discrete_env_names():  # refused here too: no device env and no LayerNorm kernel for them
+    if args.device_env and args.host_env is not None:  # refused here too: two places to step the same env
         from ._lib import PGMError
-        if args.host_env is None:
-            raise PGMError(f'{args.env_name} has discrete actions and no device environment: it runs host-stepped, '
-                           f'pass --host-env (dst: the built-in Deep Sea Treasure, or module:callable)')
+        raise PGMError('--device-env together with --host-env: the environments run on the device or on the host, '
+                       'pass one of the two')
+    if args.env_name in discrete_env_names():  # refused here too: where the env runs is chosen, no LayerNorm kernel
+        from ._lib import PGMError
+        if args.host_env is None and not args.device_env:
+            raise PGMError(f'{args.env_name} has discrete actions and no default environment: pass --host-env (dst: '
+                           f'the built-in Deep Sea Treasure on the host, or module:callable) or --device-env (Deep '
+                           f'Sea Treasure inside the fused rollout kernel)')
         if args.layernorm:
             raise PGMError(f'--layernorm with {args.env_name}: LayerNorm towers with a Categorical head are not built')
     if args.host_env is not None:  # refused here too: a spec that cannot be imported or whose env dims differ

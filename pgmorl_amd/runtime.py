@@ -13,6 +13,10 @@ the library is unavailable (no CPU fallback).
 With ``host_env`` (a ``hostenv.HostVecEnv``) the environments run on the host instead: the rollout becomes a per-step
 loop of pgm_rollout_act -> host ``step`` -> pgm_env_ingest and the evaluation a host episode loop over pgm_eval_act;
 returns, advantages and the PPO update are the same kernels on the same storage.
+
+With ``device_env=True`` on Deep Sea Treasure (the one discrete-action env with a device form) the rollout is again one
+launch, pgm_rollout_dst, and the evaluation pgm_eval_dst: the kernel sequence of the continuous device envs with the
+Categorical head and the grid world stepped inside the kernels.
 """
 import ctypes as C
 import math
@@ -21,8 +25,8 @@ import numpy as np
 import torch
 
 from . import envspec
-from ._lib import (Dims, EnvSpec, EnvState, NormState, PGMError, PPOHParams, RolloutBuf, check, launch_opts, lib,
-                   require_categorical)
+from ._lib import (Dims, DstSpec, EnvSpec, EnvState, NormState, PGMError, PPOHParams, RolloutBuf, check, launch_opts,
+                   lib, require_categorical, require_dst_device)
 from .layout import ParamLayout
 
 F32, F64, I32 = torch.float32, torch.float64, torch.int32
@@ -58,7 +62,12 @@ class TaskBatch:
                  gae_lambda=0.95, use_gae=True, use_proper_time_limits=True, ob_rms=True, obj_rms=True, raw=True,
                  clip_param=0.2, ppo_epoch=10, num_mini_batch=32, value_loss_coef=0.5, entropy_coef=0.0,
                  max_grad_norm=0.5, adam_eps=1e-5, use_clipped_value_loss=True, device='cuda', capacity=None,
-                 layernorm=False, host_env=None):
+                 layernorm=False, host_env=None, device_env=False, *, max_steps=None, time_limit_is_bad=False):
+        """device_env: run a discrete-action env on the device (Deep Sea Treasure: pgm_rollout_dst / pgm_eval_dst)
+        instead of on the host; for such an env exactly one of host_env and device_env=True is given.  The SynthMO envs
+        are device envs already: the flag changes nothing there.  max_steps / time_limit_is_bad: the device Deep Sea
+        Treasure's step limit (default envspec's, 50) and whether the limit is reported as a time-limit end, as
+        hostenv.DeepSeaTreasureHostVecEnv has them."""
         self.spec = envspec.make_spec(env_name)
         sp = self.spec
         self.host_env = host_env
@@ -78,15 +87,31 @@ class TaskBatch:
                            f'built for obs_dim <= {LN_MAX_OBS}; obs_dim {self.O} would need a streamed layer-1 '
                            f'LayerNorm kernel, which does not exist')
         # a discrete-action env (spec['discrete']): Categorical head, A = number of actions, one width-1 action per
-        # step, the *_cat entry points; such envs exist on the host only
+        # step, the *_cat entry points; such envs run on the host (host_env) or, opted into, on the device (device_env)
         self.discrete = bool(sp.get('discrete', False))
+        self.device_env = bool(device_env) and self.discrete  # (a SynthMO env is a device env with or without the flag)
         if self.discrete:
-            if host_env is None:
-                raise PGMError(f'{env_name} has discrete actions and no device environment: TaskBatch needs '
-                               f'host_env=... (hostenv.DeepSeaTreasureHostVecEnv, --host-env dst)')
+            if host_env is None and not device_env:
+                raise PGMError(f'{env_name} has discrete actions and no default device environment: TaskBatch needs '
+                               f'host_env=... (hostenv.DeepSeaTreasureHostVecEnv, --host-env dst) or device_env=True '
+                               f'(--device-env)')
+            if host_env is not None and device_env:
+                raise PGMError(f'{env_name}: host_env=... and device_env=True are two places to step the same env; '
+                               f'give exactly one')
             if self.layernorm:
                 raise PGMError(f'layernorm=True with {env_name}: LayerNorm towers with a Categorical head are not built')
             require_categorical()
+        if self.device_env:
+            if (self.O, self.A, self.K) != (3, 4, 2):
+                raise PGMError(f'device_env=True with {env_name}: the one discrete-action device env is Deep Sea '
+                               f'Treasure (obs 3, 4 actions, 2 objectives)')
+            if not 1 <= eval_num <= self.HOST_EVAL_MAX:
+                raise PGMError(f'device_env=True evaluates 1..{self.HOST_EVAL_MAX} episodes per task in one launch '
+                               f'(eval_num={eval_num})')
+            require_dst_device()
+            self.max_steps = int(max_steps or sp['max_episode_steps'])
+            self.time_limit_is_bad = bool(time_limit_is_bad)
+            self.c_dst = DstSpec(self.max_steps, int(self.time_limit_is_bad))
         self.act_width = 1 if self.discrete else self.A
         self.layout = ParamLayout(self.O, self.A, self.K, self.H, layernorm=self.layernorm, discrete=self.discrete)
         L, O, A, K, N, T = self.layout.total, self.O, self.A, self.K, self.N, self.T
@@ -152,6 +177,8 @@ class TaskBatch:
         self.last_fail_word = 0
         if host_env is not None:
             self._host_alloc(Pc)
+        if self.device_env:  # the constant raw reset observation of (row, col, step) = (0, 0, 0), for pgm_env_ingest(-1)
+            self._dst_obs0 = torch.zeros(Pc, N, O, dtype=F64, device=self.dev)
         self.set_active(P)
         self.reset_stats()
 
@@ -386,6 +413,12 @@ class TaskBatch:
         if self.host_env is not None:  # one H2D copy of the host envs' reset observations, then the ingest kernel
             self._ingest(-1, self.host_env.reset())
             return self.obs[:, 0]
+        if self.device_env:  # every env at (0, 0, 0); VecNormalize.reset on the constant reset observation
+            self.s.zero_()
+            check(lib().pgm_env_ingest(C.byref(self.dims), C.byref(self.c_state), C.byref(self.c_norm),
+                                       C.byref(self.c_rb), -1, _ptr(self._dst_obs0), None, None, None, None,
+                                       _stream()), 'pgm_env_ingest')
+            return self.obs[:, 0]
         out = torch.empty(self.P, self.N, self.O, dtype=F32, device=self.dev)
         check(lib().pgm_env_reset(C.byref(self.dims), C.byref(self.c_spec), C.byref(self.c_state),
                                   C.byref(self.c_norm), _ptr(out), _stream()), 'pgm_env_reset')
@@ -398,6 +431,9 @@ class TaskBatch:
         if self.host_env is not None:
             raise PGMError('env_step: this batch is in host-env mode (TaskBatch(host_env=...)): the environments are '
                            'stepped on the host inside rollout(), there is no device env to step')
+        if self.device_env:
+            raise PGMError('env_step: the device Deep Sea Treasure is stepped inside pgm_rollout_dst / pgm_eval_dst; '
+                           'there is no single-step kernel (pgm_dst_transition evaluates the rule on the host)')
         P, N, O, K = self.P, self.N, self.O, self.K
         action = action.to(device=self.dev, dtype=F32).contiguous()
         obs = torch.empty(P, N, O, dtype=F32, device=self.dev)
@@ -433,6 +469,11 @@ class TaskBatch:
             if noise is not self.noise:
                 self.noise.copy_(noise.to(dtype=F32))
             nz = self.noise
+        if self.device_env:  # noise: uniforms [T][N]; None: the kernel draws pgm_uniform_noise's stream of `seed`
+            check(lib().pgm_rollout_dst(C.byref(self.dims), _ptr(self.params), C.byref(self.c_dst),
+                                        C.byref(self.c_state), C.byref(self.c_norm), C.byref(self.c_rb), _ptr(nz),
+                                        C.c_uint64(seed), int(carry), _stream()), 'pgm_rollout_dst')
+            return
         check(lib().pgm_rollout(C.byref(self.dims), _ptr(self.params), C.byref(self.c_spec), C.byref(self.c_state),
                                 C.byref(self.c_norm), C.byref(self.c_rb), _ptr(nz), C.c_uint64(seed),
                                 int(carry), C.byref(launch_opts()), _stream()), 'pgm_rollout')
@@ -513,6 +554,11 @@ class TaskBatch:
         out = self.objs if out is None else out
         if self.host_env is not None:
             return self._host_evaluate(mean, var, out)
+        if self.device_env:
+            check(lib().pgm_eval_dst(C.byref(self.dims), _ptr(self.params), C.byref(self.c_dst), _ptr(mean), _ptr(var),
+                                     self.eval_num, int(self.use_ob_rms), int(self.raw), self.gamma, _ptr(out),
+                                     _stream()), 'pgm_eval_dst')
+            return out
         check(lib().pgm_eval(C.byref(self.dims), _ptr(self.params), C.byref(self.c_spec), _ptr(mean), _ptr(var),
                              _ptr(self.s0_eval), self.eval_num, int(self.use_ob_rms), int(self.raw), self.gamma,
                              _ptr(out), C.byref(launch_opts()), _stream()), 'pgm_eval')
@@ -548,7 +594,9 @@ class TaskBatch:
         (which the next rollout has not advanced yet)."""
         if self.host_env is not None:
             overlap_eval = False
-        if noise is None:  # perf mode: the counter stream of iteration j, drawn by one wide kernel up front
+        # perf mode: the counter stream of iteration j, drawn by one wide kernel up front (the fused Deep Sea Treasure
+        # rollout draws the same stream inside the kernel: noise stays None)
+        if noise is None and not self.device_env:
             self._draw_noise(j)
             noise = self.noise
         perm_ready = None
@@ -591,9 +639,11 @@ class TaskBatch:
             # the timeout word of this update, folded off the main stream, then the next update's workspace reset
             # (the next update waits for this stream: perm_ready)
             self.fold_update_flag()
-            check(lib().pgm_ppo_update_reset(C.byref(self.dims), _ptr(self.update_ws), _stream()),
-                  'pgm_ppo_update_reset')
-            self._reset_pending = True
+            if not self.discrete:  # (pgm_ppo_update_cat resets its own, smaller workspace inside the call:
+                # pgm_ppo_update_reset clears the exchange slots of pgm_ppo_update's layout, which it does not have)
+                check(lib().pgm_ppo_update_reset(C.byref(self.dims), _ptr(self.update_ws), _stream()),
+                      'pgm_ppo_update_reset')
+                self._reset_pending = True
             out = self.evaluate(self._eval_mean, self._eval_var, out=objs_out)
             out.record_stream(side)
             self._eval_done = torch.cuda.Event()

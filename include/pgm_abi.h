@@ -130,12 +130,13 @@ extern "C" {
 /* pgm_abi_features() bits: additions that leave PGM_ABI_VERSION / PGM_ABI_MINOR alone are discovered here. */
 #define PGM_FEATURE_CATEGORICAL 1 /* the *_cat entry points, pgm_param_layout_cat, pgm_uniform_noise */
 #define PGM_FEATURE_DST_DEVICE 2  /* pgm_rollout_dst, pgm_eval_dst, pgm_dst_transition: Deep Sea Treasure on the device */
+#define PGM_FEATURE_DUMMY_DEVICE 4 /* pgm_rollout_dummy, pgm_eval_dummy, pgm_dummy_transition; the dim sets 6/2/2, 6/2/3 */
 
 typedef void* pgm_stream_t; /* a hipStream_t (0 = the null stream) */
 
 /* LN (ABI 5): 0 = plain tanh towers, 1 = LayerNorm towers (params / Adam vectors in the pgm_param_layout_ln layout).
- * LN = 1 is built for obs_dim <= 32 (17/6/2, 11/3/2, 11/3/3, 27/8/2, 8/2/2); with 376/17/2 every entry point that
- * touches the policy returns PGM_E_UNSUPPORTED.  pgm_launch_opts is ignored for LN = 1 (one kernel family). */
+ * LN = 1 is built for obs_dim <= 32 (17/6/2, 11/3/2, 11/3/3, 27/8/2, 8/2/2, 6/2/2, 6/2/3); with 376/17/2 every entry
+ * point that touches the policy returns PGM_E_UNSUPPORTED.  pgm_launch_opts is ignored for LN = 1 (one kernel family). */
 typedef struct pgm_dims {
     int32_t P, N, T, O, A, K, H;
     int32_t LN;
@@ -458,6 +459,68 @@ int pgm_dst_transition(const pgm_dst_spec* spec, int32_t n, const int32_t* row, 
                        const int32_t* step, const int32_t* action, int32_t* row_out, int32_t* col_out,
                        int32_t* step_out, double* raw_obs_out, double* obj_out, double* reward_out, int32_t* done_out,
                        int32_t* bad_out);
+
+/* ---- MO-Dummy-v0 / MO-Dummy3-v0 on the device (pgm_abi_features() & PGM_FEATURE_DUMMY_DEVICE).  The reference's
+ * environments/dummy_mo_env.py:57-148 (registered with max_steps 500, environments/__init__.py:4-16): continuous
+ * actions, obs 6, act 2, 2 or 3 objectives, Gaussian head.  With that bit the dim sets (6, 2, 2) and (6, 2, 3) are
+ * accepted by every Gaussian entry point (pgm_act_forward, pgm_rollout_act, pgm_env_ingest, pgm_eval_act, pgm_gae,
+ * pgm_adv_normalize, pgm_ppo_update, plain and LayerNorm towers).
+ * State of one env: pos[2], vel[2], total_distance, total_energy (fp64) and an integer step; the raw observation is
+ * those six fp64 values (never rounded through fp32).  One step with the policy's raw fp32 action a:
+ *   ac = clip((double)a, -1, 1); last = pos; vel = (vel + ac * 0.1) * 0.95; pos = pos + vel; step += 1
+ *   step_distance = sqrt(dx*dx + dy*dy) with d = pos - last; step_energy = sqrt(ac0*ac0 + ac1*ac1); totals accumulate
+ *   obj0 = step_distance; obj1 = 1 / (step_energy + 0.1); obj2 = bound - |pos| (K = 3); reward = obj0 + 0.1 * obj1
+ *   done = step >= max_steps || |pos| > bound; bad = time_limit_is_bad && done && step == max_steps
+ * A done env resets: vel, totals, step = 0, its episode counter e += 1 and pos = reset_table[env][e mod R]; the
+ * returned observation is the reset state, the objectives, reward and flags are the terminal step's.  The reference
+ * draws the reset position from numpy's unseeded global stream; the table (envspec.dummy_reset_table) restates it
+ * reproducibly.  No product is contracted into an fma: the rule gives the same bits on the host and on the device.  It
+ * is ONE inline function (pgmorl_amd/csrc/pgm_dummy.hpp) used by the two kernels and by pgm_dummy_transition.
+ * Validation before any device work: NULL pointers (PGM_E_INVALID_ARG), the dims, the dim set (PGM_E_UNSUPPORTED),
+ * LN (as pgm_act_forward), T <= 0 (PGM_E_SHAPE), eval_num outside 1..8, max_steps <= 0, bound <= 0, R < 1,
+ * reset_count below the rows the call reads (PGM_E_INVALID_ARG). */
+typedef struct pgm_dummy_spec {
+    int32_t max_steps;         /* episode step limit (the registration's: 500) */
+    int32_t time_limit_is_bad; /* 1 (the registration's TimeLimitMask): an end on the limit step is a time-limit end
+                                  (bad_transition); 0: every end is a termination */
+    double bound;              /* radius of the disc the env must stay in (the env's: 5.0) */
+    const double* reset_table; /* [reset_count][R][2] fp64 reset positions; a device pointer for the kernels, a host
+                                  pointer for pgm_dummy_transition */
+    int32_t R;                 /* reset positions per env; episode e starts at entry e mod R */
+    int32_t reset_count;       /* rows of the table: >= N (rollout), >= eval_num (evaluation) */
+} pgm_dummy_spec;
+
+/* T rollout steps of every task in one launch (morl/mopg.py:103-135 with the env, DummyVecEnv's auto-reset and
+ * VecNormalize.step_wait on the device): per step Policy.act on rb->obs[p][t] (value, action = noise * exp(logstd) +
+ * mean, log-prob summed over the 2 actions in index order, the raw action into rb->actions), the transition of every
+ * env, the running statistics (the scalar reward feeds VecNormalize.ret / ret_rms), insert into slot t + 1; then the
+ * bootstrap value into rb->values[p][T].  Writes what T pgm_rollout_act / pgm_env_ingest pairs plus
+ * pgm_rollout_act(T) write, bit for bit.  st->s [P][N][6] holds the six state values, st->elapsed [P][N] the step,
+ * episode [P][N] the episode counters (all read and written back); st->s0 is not read and may be NULL.  Env n of every
+ * task uses row n of the reset table.  noise [T][N][2] shared by the tasks, or NULL: element (t, n, a) is then element
+ * (t * N + n) * 2 + a of pgm_normal_noise's stream of `seed`, drawn in the kernel.  carry != 0: slot T -> slot 0 first
+ * (storage.py:71-75).  rb->returns / adv are not touched.  A fresh run starts from pos = reset_table[n][0], everything
+ * else 0, and pgm_env_ingest(t = -1) on that observation. */
+int pgm_rollout_dummy(const pgm_dims* d, const float* params, const pgm_dummy_spec* env, const pgm_env_state* st,
+                      int32_t* episode, const pgm_norm_state* ns, const pgm_rollout_buf* rb, const float* noise,
+                      uint64_t seed, int32_t carry, pgm_stream_t stream);
+
+/* evaluation() (morl/mopg.py:25-46): eval_num (1..8) episodes per task, episode e from pos = reset_table[e][0], with
+ * the mean action on the raw fp64 observation normalised with the frozen ob_mean / ob_var [P][6] (use_ob_rms); per
+ * episode acc += disc * obj, disc *= gamma unless raw; an ended episode stands still; objs_out [P][K] fp64 = sum over
+ * the episodes in index order / eval_num.  pgm_dims.N and T are ignored. */
+int pgm_eval_dummy(const pgm_dims* d, const float* params, const pgm_dummy_spec* env, const double* ob_mean,
+                   const double* ob_var, int32_t eval_num, int32_t use_ob_rms, int32_t raw, double gamma,
+                   double* objs_out, pgm_stream_t stream);
+
+/* The env rule on n (state, action) pairs, on the HOST: launches nothing, needs no device, every pointer a host
+ * pointer (spec->reset_table included).  K = 2 or 3.  Inputs: state [n][6], step / episode [n], env [n] (the pair's row
+ * of the reset table, in [0, reset_count)), action fp32 [n][2].  Outputs: the state after the auto-reset (= the raw
+ * observation) state_out [n][6], step_out / episode_out [n], obj_out [n][K], reward_out [n], done_out / bad_out [n]. */
+int pgm_dummy_transition(const pgm_dummy_spec* spec, int32_t K, int32_t n, const double* state, const int32_t* step,
+                         const int32_t* episode, const int32_t* env, const float* action, double* state_out,
+                         int32_t* step_out, int32_t* episode_out, double* obj_out, double* reward_out,
+                         int32_t* done_out, int32_t* bad_out);
 
 #ifdef __cplusplus
 }

@@ -68,6 +68,13 @@ class DstSpec(C.Structure):
     _fields_ = [('max_steps', I32), ('time_limit_is_bad', I32)]
 
 
+class DummySpec(C.Structure):
+    """pgm_dummy_spec: the MO-Dummy env's step limit, how an end on the limit step is reported, the disc radius and the
+    reset table [reset_count][R][2] fp64."""
+    _fields_ = [('max_steps', I32), ('time_limit_is_bad', I32), ('bound', F64), ('reset_table', P_), ('R', I32),
+                ('reset_count', I32)]
+
+
 class LaunchOpts(C.Structure):
     """pgm_launch_opts (pgm_abi.h): which kernel family an entry point may launch; all zero = automatic."""
     _fields_ = [(n, I32) for n in ('update_kernel', 'update_split', 'fs_one_per_cu', 'rollout_kernel', 'eval_kernel',
@@ -140,16 +147,24 @@ _SIGS = {
                                   C.POINTER(RolloutBuf), P_, C.c_uint64, I32, P_]),
     'pgm_eval_dst': (C.c_int, [C.POINTER(Dims), P_, C.POINTER(DstSpec), P_, P_, I32, I32, I32, F64, P_, P_]),
     'pgm_dst_transition': (C.c_int, [C.POINTER(DstSpec), I32] + [P_] * 12),
+    # the MO-Dummy envs on the device (pgm_abi_features() & FEATURE_DUMMY_DEVICE)
+    'pgm_rollout_dummy': (C.c_int, [C.POINTER(Dims), P_, C.POINTER(DummySpec), C.POINTER(EnvState), P_,
+                                    C.POINTER(NormState), C.POINTER(RolloutBuf), P_, C.c_uint64, I32, P_]),
+    'pgm_eval_dummy': (C.c_int, [C.POINTER(Dims), P_, C.POINTER(DummySpec), P_, P_, I32, I32, I32, F64, P_, P_]),
+    'pgm_dummy_transition': (C.c_int, [C.POINTER(DummySpec), I32, I32] + [P_] * 12),
 }
 # the symbols a library of the same ABI version and minor may lack: discovered through pgm_abi_features
 FEATURE_CATEGORICAL = 1
 FEATURE_DST_DEVICE = 2
+FEATURE_DUMMY_DEVICE = 4
 _FEATURE_SYMBOLS = {'pgm_abi_features': 0, 'pgm_param_layout_cat': FEATURE_CATEGORICAL,
                     'pgm_act_forward_cat': FEATURE_CATEGORICAL, 'pgm_rollout_act_cat': FEATURE_CATEGORICAL,
                     'pgm_eval_act_cat': FEATURE_CATEGORICAL, 'pgm_ppo_update_cat': FEATURE_CATEGORICAL,
                     'pgm_ppo_update_cat_workspace_bytes': FEATURE_CATEGORICAL,
                     'pgm_uniform_noise': FEATURE_CATEGORICAL, 'pgm_rollout_dst': FEATURE_DST_DEVICE,
-                    'pgm_eval_dst': FEATURE_DST_DEVICE, 'pgm_dst_transition': FEATURE_DST_DEVICE}
+                    'pgm_eval_dst': FEATURE_DST_DEVICE, 'pgm_dst_transition': FEATURE_DST_DEVICE,
+                    'pgm_rollout_dummy': FEATURE_DUMMY_DEVICE, 'pgm_eval_dummy': FEATURE_DUMMY_DEVICE,
+                    'pgm_dummy_transition': FEATURE_DUMMY_DEVICE}
 
 EXPORTS = tuple(_SIGS)
 
@@ -224,6 +239,12 @@ def require_categorical():
 def require_dst_device():
     if not features() & FEATURE_DST_DEVICE:
         raise PGMError('this libpgm.so has no device Deep Sea Treasure entry points (pgm_abi_features() & 2 is clear); '
+                       'rebuild it with `python -m pgmorl_amd.build`')
+
+
+def require_dummy_device():
+    if not features() & FEATURE_DUMMY_DEVICE:
+        raise PGMError('this libpgm.so has no MO-Dummy entry points or dim sets (pgm_abi_features() & 4 is clear); '
                        'rebuild it with `python -m pgmorl_amd.build`')
 
 

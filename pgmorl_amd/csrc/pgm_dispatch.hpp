@@ -9,7 +9,8 @@ namespace pgm {
 template <int V>
 using ic = std::integral_constant<int, V>;
 
-// (O, A, K): Walker2d/HalfCheetah, Hopper-v2, Hopper-v3, Humanoid, Ant, Swimmer (SURVEY.md §8 header table).
+// (O, A, K): Walker2d/HalfCheetah, Hopper-v2, Hopper-v3, Humanoid, Ant, Swimmer (SURVEY.md §8 header table), then the
+// native MO-Dummy-v0 / MO-Dummy3-v0 (pgm_dummy.hpp).
 // f(ic<O>, ic<A>, ic<K>) -> int status.
 template <class F>
 int dispatch_dims(int O, int A, int K, const char* what, F&& f) {
@@ -19,8 +20,10 @@ int dispatch_dims(int O, int A, int K, const char* what, F&& f) {
     if (O == 376 && A == 17 && K == 2) return f(ic<376>{}, ic<17>{}, ic<2>{});
     if (O == 27 && A == 8 && K == 2) return f(ic<27>{}, ic<8>{}, ic<2>{});
     if (O == 8 && A == 2 && K == 2) return f(ic<8>{}, ic<2>{}, ic<2>{});
-    set_error("%s: unsupported dims O=%d A=%d K=%d (supported: 17/6/2, 11/3/2, 11/3/3, 376/17/2, 27/8/2, 8/2/2)",
-              what, O, A, K);
+    if (O == 6 && A == 2 && K == 2) return f(ic<6>{}, ic<2>{}, ic<2>{});
+    if (O == 6 && A == 2 && K == 3) return f(ic<6>{}, ic<2>{}, ic<3>{});
+    set_error("%s: unsupported dims O=%d A=%d K=%d (supported: 17/6/2, 11/3/2, 11/3/3, 376/17/2, 27/8/2, 8/2/2, 6/2/2, "
+              "6/2/3)", what, O, A, K);
     return PGM_E_UNSUPPORTED;
 }
 
@@ -75,7 +78,8 @@ inline int check_ln(const pgm_dims* d, const char* what) {
         return PGM_E_INVALID_ARG;
     }
     if (d->LN == 1 && d->O > 32) {
-        set_error("%s: LayerNorm towers are built for obs_dim <= 32 (17/6/2, 11/3/2, 11/3/3, 27/8/2, 8/2/2); obs_dim %d "
+        set_error("%s: LayerNorm towers are built for obs_dim <= 32 (17/6/2, 11/3/2, 11/3/3, 27/8/2, 8/2/2, 6/2/2, 6/2/3); obs_dim "
+                  "%d "
                   "(MO-Humanoid) needs a streamed layer-1 LayerNorm kernel that does not exist", what, d->O);
         return PGM_E_UNSUPPORTED;
     }

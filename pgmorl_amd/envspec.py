@@ -72,15 +72,47 @@ def discrete_env_names():
     return sorted(_DISCRETE_ENVS)
 
 
+# Native continuous-action envs: env id -> (obs_dim, act_dim, obj_num, max_episode_steps, bound).  The reference's
+# MuJoCo-free test env (environments/dummy_mo_env.py:57-148, registered with max_steps 500 in
+# environments/__init__.py:4-16): its real dynamics, not a SynthMO stand-in, stepped inside the fused kernels of
+# csrc/pgm_dummy.hip (the default) or on the host (hostenv.DummyMOHostVecEnv); Gaussian head.
+_NATIVE_ENVS = {
+    'MO-Dummy-v0': (6, 2, 2, 500, 5.0),
+    'MO-Dummy3-v0': (6, 2, 3, 500, 5.0),
+}
+DUMMY_RESETS = 256  # R: reset positions per env seed (dummy_reset_table)
+DUMMY_RESET_STREAM = 0xD0330000  # the splitmix64 stream constant of the reset positions (reset_state: 0x5EED0000)
+
+
+def native_env_names():
+    return sorted(_NATIVE_ENVS)
+
+
+def dummy_reset_table(seed, count, R=DUMMY_RESETS):
+    """[count][R][2] fp64 reset positions of the MO-Dummy envs: entry (i, r) = 2 u - 1 with u the splitmix64 uniforms
+    of env seed ``seed + i``.  The reference draws np.random.uniform(-1, 1, 2) from numpy's global stream at every
+    reset, which is not reproducible per env; this table is a deliberate restatement of that unseeded draw.  A training
+    env n starts its episode e at entry (n, e mod R); evaluation episode e starts at entry (e, 0)."""
+    if R < 1:
+        raise ValueError(f'dummy_reset_table: R = {R} reset positions per env must be at least 1')
+    return np.stack([(2.0 * _uniforms(DUMMY_RESET_STREAM + int(seed) + i, 2 * R) - 1.0).reshape(R, 2)
+                     for i in range(count)])
+
+
 def make_spec(env_name):
     """Constant arrays of one SynthMO env (all fp64); for a discrete-action env the dims alone, with
-    ``discrete = True`` and ``act_dim`` the number of actions."""
+    ``discrete = True`` and ``act_dim`` the number of actions; for a native env the dims, ``bound``, the action clip
+    and ``native`` (no SynthMO arrays)."""
+    if env_name in _NATIVE_ENVS:
+        O, A, K, tmax, bound = _NATIVE_ENVS[env_name]
+        return {'name': env_name, 'obs_dim': O, 'act_dim': A, 'obj_num': K, 'max_episode_steps': tmax, 'bound': bound,
+                'act_lo': np.full(A, -1.0), 'act_hi': np.full(A, 1.0), 'native': 'dummy'}
     if env_name in _DISCRETE_ENVS:
         O, A, K, tmax = _DISCRETE_ENVS[env_name]
         return {'name': env_name, 'obs_dim': O, 'act_dim': A, 'obj_num': K, 'max_episode_steps': tmax,
                 'discrete': True}
     if env_name not in _ENVS:
-        raise ValueError(f'unknown env {env_name!r}; known: {env_names() + discrete_env_names()}')
+        raise ValueError(f'unknown env {env_name!r}; known: {env_names() + discrete_env_names() + native_env_names()}')
     O, A, K, tmax, (lo, hi), objrows = _ENVS[env_name]
     u = _uniforms(SPEC_SEED, O + O * A + O + K * O)
     p = 0

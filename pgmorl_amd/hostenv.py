@@ -9,6 +9,8 @@ fp64 observations, the scalar env reward, ``info['obj']`` and the done / bad_tra
 * ``SynthHostVecEnv``  SynthMO (envspec.py) in numpy fp64: the stand-in that exercises the whole path without MuJoCo.
 * ``DeepSeaTreasureHostVecEnv``  Deep Sea Treasure (``--host-env dst``), the discrete-action grid world of the reference's
                        shipped run, vectorised numpy.
+* ``DummyMOHostVecEnv``  MO-Dummy-v0 / MO-Dummy3-v0 (``--host-env dummy``), the reference's MuJoCo-free continuous env,
+                       vectorised numpy with the device env's operation order.
 * ``GymHostVecEnv``    any ``make_env(env_name, seed, rank)`` returning gym-style objects (duck-typed: gym itself is
                        never imported here), in the 4-tuple or the 5-tuple step API.
 """
@@ -73,6 +75,8 @@ class SynthHostVecEnv(HostVecEnv):
         sp = envspec.make_spec(env_name)
         if sp.get('discrete'):
             raise ValueError(f'{env_name} has discrete actions and no SynthMO stand-in (use --host-env dst)')
+        if sp.get('native'):
+            raise ValueError(f'{env_name} is a native env with no SynthMO stand-in (use --host-env {sp["native"]})')
         self.spec = sp
         self.env_name, self.seed = env_name, seed
         self.capacity = self.P = P
@@ -221,6 +225,108 @@ class DeepSeaTreasureHostVecEnv(HostVecEnv):
         return self._obs(self._est), np.stack([val, fuel], axis=-1), self._edone.copy()
 
 
+class DummyMOHostVecEnv(HostVecEnv):
+    """MO-Dummy-v0 / MO-Dummy3-v0 (obs 6, act 2, 2 or 3 objectives; the reference's environments/dummy_mo_env.py:57-148),
+    P x N envs in numpy fp64.  The rule of csrc/pgm_dummy.hpp, every operation elementwise in the same order (no dot
+    products or norms whose summation order numpy chooses), so that the fp64 outputs are the device's bit for bit:
+
+        ac = clip(a, -1, 1); last = pos; vel = (vel + ac * 0.1) * 0.95; pos = pos + vel; step += 1
+        step_distance = sqrt(dx*dx + dy*dy), d = pos - last; step_energy = sqrt(ac0*ac0 + ac1*ac1); totals accumulate
+        obj = [step_distance, 1 / (step_energy + 0.1), bound - |pos| (3 objectives)]; reward = obj0 + 0.1 * obj1
+        done = step >= max_steps or |pos| > bound; bad = time_limit_is_bad and done and step == max_steps
+
+    The raw observation is [pos, vel, total_distance, total_energy] in fp64.  A done env resets to the next position
+    of its row of envspec.dummy_reset_table (episode e of env n: entry (n, e mod R)); evaluation episode e starts at
+    entry (e, 0) of the table of eval_num seeds."""
+
+    def __init__(self, env_name='MO-Dummy-v0', P=1, N=1, seed=0, max_steps=None, bound=None, time_limit_is_bad=True,
+                 R=None):
+        sp = envspec.make_spec(env_name)
+        if sp.get('native') != 'dummy':
+            raise ValueError(f'{env_name} is not an MO-Dummy env ({envspec.native_env_names()})')
+        self.env_name, self.seed = env_name, seed
+        self.capacity = self.P = P
+        self.N = N
+        self.obs_dim, self.act_dim, self.obj_num = sp['obs_dim'], sp['act_dim'], sp['obj_num']
+        self.max_steps = int(max_steps or sp['max_episode_steps'])
+        self.bound = float(sp['bound'] if bound is None else bound)
+        self.time_limit_is_bad = bool(time_limit_is_bad)
+        self.R = int(envspec.DUMMY_RESETS if R is None else R)
+        self.resets = envspec.dummy_reset_table(seed, N, self.R)  # [N, R, 2]: env n of every task
+        self._st = self._est = None  # {'s': f64 [P, N, 6], 'step': i64 [P, N], 'episode': i64 [P, N]}
+        self._edone = None
+
+    def set_active(self, P):
+        if not 0 < P <= self.capacity:
+            raise ValueError(f'active tasks {P} outside [1, {self.capacity}]')
+        self.P = P
+        self._st = None
+
+    def _fresh(self, pos):
+        s = np.zeros(pos.shape[:2] + (6,))
+        s[..., :2] = pos
+        return {'s': s, 'step': np.zeros(pos.shape[:2], dtype=np.int64),
+                'episode': np.zeros(pos.shape[:2], dtype=np.int64)}
+
+    def _move(self, st, actions, frozen=None):
+        """One step of every env not in ``frozen`` -> (obj [.., K], reward, done, on the limit step)."""
+        s = st['s']
+        a = np.asarray(actions, dtype=np.float32).astype(np.float64)
+        ac0, ac1 = np.clip(a[..., 0], -1.0, 1.0), np.clip(a[..., 1], -1.0, 1.0)
+        lx, ly = s[..., 0], s[..., 1]
+        vx = (s[..., 2] + ac0 * 0.1) * 0.95
+        vy = (s[..., 3] + ac1 * 0.1) * 0.95
+        px, py = lx + vx, ly + vy
+        dx, dy = px - lx, py - ly
+        dist = np.sqrt(dx * dx + dy * dy)
+        energy = np.sqrt(ac0 * ac0 + ac1 * ac1)
+        r = np.sqrt(px * px + py * py)
+        new = np.stack([px, py, vx, vy, s[..., 4] + dist, s[..., 5] + energy], axis=-1)
+        step = st['step'] + 1
+        obj = [dist, 1.0 / (energy + 0.1)]
+        if self.obj_num == 3:
+            obj.append(self.bound - r)
+        obj = np.stack(obj, axis=-1)
+        reward = obj[..., 0] + 0.1 * obj[..., 1]
+        done = (step >= self.max_steps) | (r > self.bound)
+        limit = step == self.max_steps
+        if frozen is not None:
+            new, step = np.where(frozen[..., None], s, new), np.where(frozen, st['step'], step)
+            obj, reward = np.where(frozen[..., None], 0.0, obj), np.where(frozen, 0.0, reward)
+            done, limit = done & ~frozen, limit & ~frozen
+        st['s'], st['step'] = new, step
+        return obj, reward, done, limit
+
+    def reset(self):
+        self._st = self._fresh(np.broadcast_to(self.resets[:, 0], (self.P, self.N, 2)))
+        return self._st['s'].copy()
+
+    def step(self, actions):
+        st = self._st
+        obj, reward, done, limit = self._move(st, actions)
+        bad = done & limit if self.time_limit_is_bad else np.zeros_like(done)
+        if done.any():  # DummyVecEnv auto-reset: the returned observation is the next episode's first
+            st['episode'] = st['episode'] + done
+            n = np.broadcast_to(np.arange(self.N), done.shape)
+            pos = self.resets[n, st['episode'] % self.R]
+            fresh = np.zeros_like(st['s'])
+            fresh[..., :2] = pos
+            st['s'] = np.where(done[..., None], fresh, st['s'])
+            st['step'] = np.where(done, 0, st['step'])
+        return st['s'].copy(), reward, done, bad, obj
+
+    def eval_reset(self, eval_num):
+        tab = envspec.dummy_reset_table(self.seed, eval_num, self.R)
+        self._est = self._fresh(np.broadcast_to(tab[:, 0], (self.P, eval_num, 2)))
+        self._edone = np.zeros((self.P, eval_num), dtype=bool)
+        return self._est['s'].copy()
+
+    def eval_step(self, actions):
+        obj, _, done, _ = self._move(self._est, actions, frozen=self._edone)  # ended episodes stand still
+        self._edone = self._edone | done
+        return self._est['s'].copy(), obj, self._edone.copy()
+
+
 def _reset_obs(r):
     """env.reset(): obs (old API) or (obs, info) (new API)."""
     if isinstance(r, tuple) and len(r) == 2 and isinstance(r[1], dict):
@@ -350,15 +456,17 @@ class GymHostVecEnv(HostVecEnv):
 
 def resolve(spec):
     """``--host-env SPEC`` -> factory(env_name, P, N, seed) of a HostVecEnv.  ``synth``: SynthHostVecEnv; ``dst``:
-    DeepSeaTreasureHostVecEnv; ``module:callable``: GymHostVecEnv over ``callable(env_name, seed, rank)``.  Raises ValueError for a spec that
-    cannot be imported."""
+    DeepSeaTreasureHostVecEnv; ``dummy``: DummyMOHostVecEnv (the MO-Dummy envs only); ``module:callable``:
+    GymHostVecEnv over ``callable(env_name, seed, rank)``.  Raises ValueError for a spec that cannot be imported."""
     if spec == 'synth':
         return SynthHostVecEnv
     if spec == 'dst':
         return DeepSeaTreasureHostVecEnv
+    if spec == 'dummy':
+        return DummyMOHostVecEnv
     mod, sep, name = str(spec).partition(':')
     if not sep or not mod or not name:
-        raise ValueError(f'--host-env {spec!r}: expected "synth", "dst" or "module:callable"')
+        raise ValueError(f'--host-env {spec!r}: expected "synth", "dst", "dummy" or "module:callable"')
     try:
         fn = getattr(importlib.import_module(mod), name)
     except (ImportError, AttributeError) as e:
@@ -373,6 +481,8 @@ def check_spec(spec, env_name, seed=0):
     (the kernels are compiled for those dims).  Returns the factory."""
     factory = resolve(spec)
     want = envspec.make_spec(env_name)
+    if spec == 'dummy' and want.get('native') != 'dummy':
+        raise ValueError(f'--host-env dummy steps the MO-Dummy envs only ({envspec.native_env_names()}), not {env_name}')
     want = (want['obs_dim'], want['act_dim'], want['obj_num'])
     probe = factory(env_name, 1, 1, seed)
     try:

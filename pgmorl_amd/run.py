@@ -63,7 +63,8 @@ def get_parser():
     add('--device', default='cuda')
     add('--host-env', default=None, metavar='SPEC',
         help='step the environments on the host (policy, VecNormalize, storage and PPO stay on the device): '
-             '"synth" (SynthMO in numpy) or "module:callable" with callable(env_name, seed, rank) -> a gym-style '
+             '"synth" (SynthMO in numpy), "dummy" (the MO-Dummy envs, which otherwise run on the device) or '
+             '"module:callable" with callable(env_name, seed, rank) -> a gym-style '
              'multi-objective env; default: the device envs')
     add('--device-env', action='store_true', default=False,
         help='run a discrete-action env on the device (MO-DeepSeaTreasure-v0: the fused Categorical rollout and '

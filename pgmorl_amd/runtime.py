@@ -17,6 +17,10 @@ returns, advantages and the PPO update are the same kernels on the same storage.
 With ``device_env=True`` on Deep Sea Treasure (the one discrete-action env with a device form) the rollout is again one
 launch, pgm_rollout_dst, and the evaluation pgm_eval_dst: the kernel sequence of the continuous device envs with the
 Categorical head and the grid world stepped inside the kernels.
+
+The MO-Dummy envs (envspec.native_env_names(): the reference's MuJoCo-free continuous env) are device envs by default,
+like SynthMO: the rollout is pgm_rollout_dummy, the evaluation pgm_eval_dummy, everything else the Gaussian kernels.
+``host_env=hostenv.DummyMOHostVecEnv(...)`` selects the host-stepped path instead.
 """
 import ctypes as C
 import math
@@ -25,8 +29,8 @@ import numpy as np
 import torch
 
 from . import envspec
-from ._lib import (Dims, DstSpec, EnvSpec, EnvState, NormState, PGMError, PPOHParams, RolloutBuf, check, launch_opts,
-                   lib, require_categorical, require_dst_device)
+from ._lib import (Dims, DstSpec, DummySpec, EnvSpec, EnvState, NormState, PGMError, PPOHParams, RolloutBuf, check,
+                   launch_opts, lib, require_categorical, require_dst_device, require_dummy_device)
 from .layout import ParamLayout
 
 F32, F64, I32 = torch.float32, torch.float64, torch.int32
@@ -62,12 +66,16 @@ class TaskBatch:
                  gae_lambda=0.95, use_gae=True, use_proper_time_limits=True, ob_rms=True, obj_rms=True, raw=True,
                  clip_param=0.2, ppo_epoch=10, num_mini_batch=32, value_loss_coef=0.5, entropy_coef=0.0,
                  max_grad_norm=0.5, adam_eps=1e-5, use_clipped_value_loss=True, device='cuda', capacity=None,
-                 layernorm=False, host_env=None, device_env=False, *, max_steps=None, time_limit_is_bad=False):
+                 layernorm=False, host_env=None, device_env=False, *, max_steps=None, time_limit_is_bad=None,
+                 bound=None, R=None):
         """device_env: run a discrete-action env on the device (Deep Sea Treasure: pgm_rollout_dst / pgm_eval_dst)
         instead of on the host; for such an env exactly one of host_env and device_env=True is given.  The SynthMO envs
         are device envs already: the flag changes nothing there.  max_steps / time_limit_is_bad: the device Deep Sea
         Treasure's step limit (default envspec's, 50) and whether the limit is reported as a time-limit end, as
-        hostenv.DeepSeaTreasureHostVecEnv has them."""
+        hostenv.DeepSeaTreasureHostVecEnv has them.  An MO-Dummy env is a device env by default (device_env changes
+        nothing); max_steps (default 500), bound (5.0), time_limit_is_bad (here default True: the registration's
+        TimeLimitMask) and R (reset positions per env, default envspec.DUMMY_RESETS) are the device env's, as
+        hostenv.DummyMOHostVecEnv has them."""
         self.spec = envspec.make_spec(env_name)
         sp = self.spec
         self.host_env = host_env
@@ -112,6 +120,23 @@ class TaskBatch:
             self.max_steps = int(max_steps or sp['max_episode_steps'])
             self.time_limit_is_bad = bool(time_limit_is_bad)
             self.c_dst = DstSpec(self.max_steps, int(self.time_limit_is_bad))
+        # an MO-Dummy env stepped inside pgm_rollout_dummy / pgm_eval_dummy (the default for these envs)
+        self.dummy_env = sp.get('native') == 'dummy' and host_env is None
+        if sp.get('native') == 'dummy':
+            require_dummy_device()  # (the dim sets 6/2/2, 6/2/3 of every Gaussian kernel come with the same bit)
+        if self.dummy_env:
+            if not 1 <= eval_num <= self.HOST_EVAL_MAX:
+                raise PGMError(f'{env_name} evaluates 1..{self.HOST_EVAL_MAX} episodes per task in one launch '
+                               f'(eval_num={eval_num})')
+            if num_processes > 8:
+                raise PGMError(f'{env_name}: num_processes={num_processes} envs per task > 8 unsupported')
+            self.max_steps = int(max_steps or sp['max_episode_steps'])
+            self.bound = float(sp['bound'] if bound is None else bound)
+            self.time_limit_is_bad = True if time_limit_is_bad is None else bool(time_limit_is_bad)
+            self.R = int(envspec.DUMMY_RESETS if R is None else R)
+            if self.max_steps <= 0 or not self.bound > 0 or self.R < 1:
+                raise PGMError(f'{env_name}: max_steps={self.max_steps}, bound={self.bound} and R={self.R} must be '
+                               f'positive')
         self.act_width = 1 if self.discrete else self.A
         self.layout = ParamLayout(self.O, self.A, self.K, self.H, layernorm=self.layernorm, discrete=self.discrete)
         L, O, A, K, N, T = self.layout.total, self.O, self.A, self.K, self.N, self.T
@@ -144,6 +169,11 @@ class TaskBatch:
         z('obj_acc', N, K, dt=F64)
         z('obj_valid', dt=I32)
         z('ret', N, dt=F64)
+        if self.dummy_env:  # per (task, env): resets since env_reset(); the reset positions [N][R][2], [eval_num][R][2]
+            z('episode', N, dt=I32)
+            self._dummy_train = torch.tensor(envspec.dummy_reset_table(seed, N, self.R), dtype=F64, device=self.dev)
+            self._dummy_eval = torch.tensor(envspec.dummy_reset_table(seed, eval_num, self.R), dtype=F64,
+                                            device=self.dev)
         # rollout storage (storage.py:12-30)
         z('obs', T + 1, N, O)
         z('actions', T, N, self.act_width)
@@ -398,6 +428,11 @@ class TaskBatch:
                                 int(self.use_obj_rms))
         self.c_rb = RolloutBuf(*(_ptr(t) for t in (self.obs, self.actions, self.logp, self.values, self.rewards,
                                                    self.masks, self.bad_masks, self.returns, self.adv)))
+        if self.dummy_env:
+            tlb = int(self.time_limit_is_bad)
+            self.c_dummy = DummySpec(self.max_steps, tlb, self.bound, _ptr(self._dummy_train), self.R, self.N)
+            self.c_dummy_eval = DummySpec(self.max_steps, tlb, self.bound, _ptr(self._dummy_eval), self.R,
+                                          self.eval_num)
 
     def reset_stats(self):
         """Fresh RunningMeanStd objects: count 1e-4, mean 0, var 1 (running_mean_std.py:5-8)."""
@@ -419,6 +454,15 @@ class TaskBatch:
                                        C.byref(self.c_rb), -1, _ptr(self._dst_obs0), None, None, None, None,
                                        _stream()), 'pgm_env_ingest')
             return self.obs[:, 0]
+        if self.dummy_env:  # env n of every task at entry (n, 0) of the reset table, at rest; VecNormalize.reset
+            self.s.zero_()
+            self.s[:, :, :2] = self._dummy_train[:, 0]
+            self.elapsed.zero_()
+            self.episode.zero_()
+            check(lib().pgm_env_ingest(C.byref(self.dims), C.byref(self.c_state), C.byref(self.c_norm),
+                                       C.byref(self.c_rb), -1, _ptr(self.s), None, None, None, None, _stream()),
+                  'pgm_env_ingest')
+            return self.obs[:, 0]
         out = torch.empty(self.P, self.N, self.O, dtype=F32, device=self.dev)
         check(lib().pgm_env_reset(C.byref(self.dims), C.byref(self.c_spec), C.byref(self.c_state),
                                   C.byref(self.c_norm), _ptr(out), _stream()), 'pgm_env_reset')
@@ -434,6 +478,9 @@ class TaskBatch:
         if self.device_env:
             raise PGMError('env_step: the device Deep Sea Treasure is stepped inside pgm_rollout_dst / pgm_eval_dst; '
                            'there is no single-step kernel (pgm_dst_transition evaluates the rule on the host)')
+        if self.dummy_env:
+            raise PGMError(f'env_step: {self.env_name} is stepped inside pgm_rollout_dummy / pgm_eval_dummy; there is '
+                           f'no single-step kernel (pgm_dummy_transition evaluates the rule on the host)')
         P, N, O, K = self.P, self.N, self.O, self.K
         action = action.to(device=self.dev, dtype=F32).contiguous()
         obs = torch.empty(P, N, O, dtype=F32, device=self.dev)
@@ -473,6 +520,12 @@ class TaskBatch:
             check(lib().pgm_rollout_dst(C.byref(self.dims), _ptr(self.params), C.byref(self.c_dst),
                                         C.byref(self.c_state), C.byref(self.c_norm), C.byref(self.c_rb), _ptr(nz),
                                         C.c_uint64(seed), int(carry), _stream()), 'pgm_rollout_dst')
+            return
+        if self.dummy_env:  # noise: normals [T][N][A]; None: the kernel draws pgm_normal_noise's stream of `seed`
+            check(lib().pgm_rollout_dummy(C.byref(self.dims), _ptr(self.params), C.byref(self.c_dummy),
+                                          C.byref(self.c_state), _ptr(self.episode), C.byref(self.c_norm),
+                                          C.byref(self.c_rb), _ptr(nz), C.c_uint64(seed), int(carry), _stream()),
+                  'pgm_rollout_dummy')
             return
         check(lib().pgm_rollout(C.byref(self.dims), _ptr(self.params), C.byref(self.c_spec), C.byref(self.c_state),
                                 C.byref(self.c_norm), C.byref(self.c_rb), _ptr(nz), C.c_uint64(seed),
@@ -559,6 +612,11 @@ class TaskBatch:
                                      self.eval_num, int(self.use_ob_rms), int(self.raw), self.gamma, _ptr(out),
                                      _stream()), 'pgm_eval_dst')
             return out
+        if self.dummy_env:
+            check(lib().pgm_eval_dummy(C.byref(self.dims), _ptr(self.params), C.byref(self.c_dummy_eval), _ptr(mean),
+                                       _ptr(var), self.eval_num, int(self.use_ob_rms), int(self.raw), self.gamma,
+                                       _ptr(out), _stream()), 'pgm_eval_dummy')
+            return out
         check(lib().pgm_eval(C.byref(self.dims), _ptr(self.params), C.byref(self.c_spec), _ptr(mean), _ptr(var),
                              _ptr(self.s0_eval), self.eval_num, int(self.use_ob_rms), int(self.raw), self.gamma,
                              _ptr(out), C.byref(launch_opts()), _stream()), 'pgm_eval')
@@ -595,8 +653,8 @@ class TaskBatch:
         if self.host_env is not None:
             overlap_eval = False
         # perf mode: the counter stream of iteration j, drawn by one wide kernel up front (the fused Deep Sea Treasure
-        # rollout draws the same stream inside the kernel: noise stays None)
-        if noise is None and not self.device_env:
+        # and MO-Dummy rollouts draw the same stream inside the kernel: noise stays None)
+        if noise is None and not self.device_env and not self.dummy_env:
             self._draw_noise(j)
             noise = self.noise
         perm_ready = None

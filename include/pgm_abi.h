@@ -127,10 +127,14 @@ extern "C" {
 #define PGM_PC_LINEAR_B 11   /* dist.linear.bias        [A] */
 #define PGM_NUM_PARAM_TENSORS_CAT 12
 
-/* pgm_abi_features() bits: additions that leave PGM_ABI_VERSION / PGM_ABI_MINOR alone are discovered here. */
+/* Feature bits: additions that leave PGM_ABI_VERSION / PGM_ABI_MINOR alone are discovered here.  pgm_abi_features()
+ * reports bits 1, 2 and 4 and its value (7) is frozen, since callers compare it for equality; pgm_abi_feature_mask()
+ * reports every bit, PGM_FEATURE_ANY_DIMS and any later one included.  New callers read pgm_abi_feature_mask() and
+ * fall back to pgm_abi_features() where a library lacks the symbol. */
 #define PGM_FEATURE_CATEGORICAL 1 /* the *_cat entry points, pgm_param_layout_cat, pgm_uniform_noise */
 #define PGM_FEATURE_DST_DEVICE 2  /* pgm_rollout_dst, pgm_eval_dst, pgm_dst_transition: Deep Sea Treasure on the device */
 #define PGM_FEATURE_DUMMY_DEVICE 4 /* pgm_rollout_dummy, pgm_eval_dummy, pgm_dummy_transition; the dim sets 6/2/2, 6/2/3 */
+#define PGM_FEATURE_ANY_DIMS 8    /* the *_any entry points (host envs of any dims); in pgm_abi_feature_mask() only */
 
 typedef void* pgm_stream_t; /* a hipStream_t (0 = the null stream) */
 
@@ -373,7 +377,8 @@ int pgm_normal_noise(int64_t n, uint64_t seed, float* out, pgm_stream_t stream);
  *
  * Storage: rb->actions is [P][T][N][1] fp32 holding the action index (exact; the reference's width-1 action tensor,
  * storage.py:19-25); every other buffer as for the Gaussian head. */
-int pgm_abi_features(void); /* bit mask of PGM_FEATURE_*; a library without this symbol has none */
+int pgm_abi_features(void); /* bit mask of PGM_FEATURE_* up to 4 (frozen at 7); a library without this symbol has none */
+int pgm_abi_feature_mask(void); /* bit mask of every PGM_FEATURE_*; a library without this symbol: pgm_abi_features() */
 
 /* offsets[PGM_NUM_PARAM_TENSORS_CAT] (floats; indices 0..9 in PGM_P_* order, then PGM_PC_LINEAR_W / _B), every tensor
  * 16-byte aligned, *total a multiple of 64 floats. */
@@ -521,6 +526,41 @@ int pgm_dummy_transition(const pgm_dummy_spec* spec, int32_t K, int32_t n, const
                          const int32_t* episode, const int32_t* env, const float* action, double* state_out,
                          int32_t* step_out, int32_t* episode_out, double* obj_out, double* reward_out,
                          int32_t* done_out, int32_t* bad_out);
+
+/* ---- Host-stepped environments of any dims (pgm_abi_feature_mask() & PGM_FEATURE_ANY_DIMS).  One kernel family compiled
+ * for dims up to (O, A, K) = (32, 8, 3) and launched with the true dims of pgm_dims: plain towers (LN = 0), H = 64,
+ * 1 <= O <= 32, 1 <= K <= 3, N <= 8; head = 0: Gaussian, 1 <= A <= 8 action dims, params in the pgm_param_layout
+ * layout; head = 1: Categorical, 2 <= A <= 8 actions, params in the pgm_param_layout_cat layout, the SAMPLING RULE
+ * above.  Every buffer has the true dims as strides (rb->obs [P][T+1][N][O], ...).  On a dim set the compiled entry
+ * points support, pgm_rollout_act_any / pgm_eval_act_any / pgm_env_ingest_any write what those write, bit for bit.
+ * Every call validates before any device work: NULL pointers, the dims (H, N), the range above (PGM_E_UNSUPPORTED
+ * naming the limit), LN != 0 (PGM_E_UNSUPPORTED), then the step index, E or the minibatch shape.
+ * pgm_gae, pgm_adv_normalize, pgm_param_layout(_cat), pgm_normal_noise, pgm_uniform_noise and pgm_randperm take
+ * runtime dims already. */
+
+/* pgm_rollout_act / pgm_rollout_act_cat.  rnd: base of [T][N][A] normals (head 0) or [T][N] uniforms (head 1);
+ * action_out: float [P][N][A] or int32_t [P][N].  t == T writes rb->values[p][T] only (rnd, action_out may be NULL). */
+int pgm_rollout_act_any(const pgm_dims* d, int32_t head, const float* params, const pgm_rollout_buf* rb, int32_t t,
+                        const float* rnd, void* action_out, pgm_stream_t stream);
+
+/* pgm_eval_act / pgm_eval_act_cat: raw_obs [P][E][O] fp64, 1 <= E <= 8; action_out float [P][E][A] or int32_t [P][E]. */
+int pgm_eval_act_any(const pgm_dims* d, int32_t head, const float* params, const double* ob_mean,
+                     const double* ob_var, int32_t use_ob_rms, const double* raw_obs, int32_t E, void* action_out,
+                     pgm_stream_t stream);
+
+/* pgm_env_ingest: t = -1 is the reset; no auto-reset; the scalar reward feeds VecNormalize.ret.  d->A is not read
+ * beyond its range check (1..8). */
+int pgm_env_ingest_any(const pgm_dims* d, const pgm_env_state* st, const pgm_norm_state* ns,
+                       const pgm_rollout_buf* rb, int32_t t, const double* raw_obs, const double* raw_obj,
+                       const double* reward, const int32_t* done, const int32_t* bad_transition, pgm_stream_t stream);
+
+/* PPO.update (arguments as pgm_ppo_update_cat) with the head's log-prob and entropy.  ppo_update_any_kernel: one
+ * 256-thread workgroup per tower, parameters and Adam moments LDS-resident; needs 2 P <= CU count (PGM_E_UNSUPPORTED
+ * otherwise).  workspace: pgm_ppo_update_any_workspace_bytes(d) caller-owned device bytes, reset inside the call. */
+int pgm_ppo_update_any(const pgm_dims* d, int32_t head, const pgm_ppo_hparams* hp, float* params, float* adam_m,
+                       float* adam_v, int32_t* adam_step, const float* lr, const int32_t* perms,
+                       const pgm_rollout_buf* rb, float* stats, void* workspace, pgm_stream_t stream);
+size_t pgm_ppo_update_any_workspace_bytes(const pgm_dims* d); /* monotone in d->P */
 
 #ifdef __cplusplus
 }

@@ -134,6 +134,7 @@ _SIGS = {
     'pgm_eval_act': (C.c_int, [C.POINTER(Dims), P_, P_, P_, I32, P_, I32, P_, P_]),
     # discrete-action policies (pgm_abi_features() & FEATURE_CATEGORICAL)
     'pgm_abi_features': (C.c_int, []),
+    'pgm_abi_feature_mask': (C.c_int, []),
     'pgm_param_layout_cat': (C.c_int, [I32, I32, I32, I32, C.POINTER(I32), C.POINTER(I32)]),
     'pgm_act_forward_cat': (C.c_int, [C.POINTER(Dims), P_, P_, P_, I32, P_, P_, P_, P_]),
     'pgm_rollout_act_cat': (C.c_int, [C.POINTER(Dims), P_, C.POINTER(RolloutBuf), I32, P_, P_, P_]),
@@ -152,19 +153,32 @@ _SIGS = {
                                     C.POINTER(NormState), C.POINTER(RolloutBuf), P_, C.c_uint64, I32, P_]),
     'pgm_eval_dummy': (C.c_int, [C.POINTER(Dims), P_, C.POINTER(DummySpec), P_, P_, I32, I32, I32, F64, P_, P_]),
     'pgm_dummy_transition': (C.c_int, [C.POINTER(DummySpec), I32, I32] + [P_] * 12),
+    # host-stepped environments of any dims (pgm_abi_feature_mask() & FEATURE_ANY_DIMS); the second argument is the head
+    'pgm_rollout_act_any': (C.c_int, [C.POINTER(Dims), I32, P_, C.POINTER(RolloutBuf), I32, P_, P_, P_]),
+    'pgm_eval_act_any': (C.c_int, [C.POINTER(Dims), I32, P_, P_, P_, I32, P_, I32, P_, P_]),
+    'pgm_env_ingest_any': (C.c_int, [C.POINTER(Dims), C.POINTER(EnvState), C.POINTER(NormState),
+                                     C.POINTER(RolloutBuf), I32, P_, P_, P_, P_, P_, P_]),
+    'pgm_ppo_update_any': (C.c_int, [C.POINTER(Dims), I32, C.POINTER(PPOHParams), P_, P_, P_, P_, P_, P_,
+                                     C.POINTER(RolloutBuf), P_, P_, P_]),
+    'pgm_ppo_update_any_workspace_bytes': (C.c_size_t, [C.POINTER(Dims)]),
 }
 # the symbols a library of the same ABI version and minor may lack: discovered through pgm_abi_features
 FEATURE_CATEGORICAL = 1
 FEATURE_DST_DEVICE = 2
 FEATURE_DUMMY_DEVICE = 4
-_FEATURE_SYMBOLS = {'pgm_abi_features': 0, 'pgm_param_layout_cat': FEATURE_CATEGORICAL,
+FEATURE_ANY_DIMS = 8
+# the range of the runtime-dim kernel family (pgm_anydims.hpp)
+ANY_MAX_OBS, ANY_MAX_ACT, ANY_MAX_OBJ = 32, 8, 3
+_FEATURE_SYMBOLS = {'pgm_abi_features': 0, 'pgm_abi_feature_mask': 0, 'pgm_param_layout_cat': FEATURE_CATEGORICAL,
                     'pgm_act_forward_cat': FEATURE_CATEGORICAL, 'pgm_rollout_act_cat': FEATURE_CATEGORICAL,
                     'pgm_eval_act_cat': FEATURE_CATEGORICAL, 'pgm_ppo_update_cat': FEATURE_CATEGORICAL,
                     'pgm_ppo_update_cat_workspace_bytes': FEATURE_CATEGORICAL,
                     'pgm_uniform_noise': FEATURE_CATEGORICAL, 'pgm_rollout_dst': FEATURE_DST_DEVICE,
                     'pgm_eval_dst': FEATURE_DST_DEVICE, 'pgm_dst_transition': FEATURE_DST_DEVICE,
                     'pgm_rollout_dummy': FEATURE_DUMMY_DEVICE, 'pgm_eval_dummy': FEATURE_DUMMY_DEVICE,
-                    'pgm_dummy_transition': FEATURE_DUMMY_DEVICE}
+                    'pgm_dummy_transition': FEATURE_DUMMY_DEVICE, 'pgm_rollout_act_any': FEATURE_ANY_DIMS,
+                    'pgm_eval_act_any': FEATURE_ANY_DIMS, 'pgm_env_ingest_any': FEATURE_ANY_DIMS,
+                    'pgm_ppo_update_any': FEATURE_ANY_DIMS, 'pgm_ppo_update_any_workspace_bytes': FEATURE_ANY_DIMS}
 
 EXPORTS = tuple(_SIGS)
 
@@ -225,8 +239,11 @@ def param_layout(O, A, K, H=64):
 
 
 def features():
-    """pgm_abi_features(): the bit mask of optional entry-point groups; a library without the symbol has none."""
+    """The bit mask of optional entry-point groups: pgm_abi_feature_mask() (every group), or pgm_abi_features() (the
+    groups up to bit 4, its value frozen) from a library without it; a library with neither symbol has none."""
     h = lib()
+    if hasattr(h, 'pgm_abi_feature_mask'):
+        return int(h.pgm_abi_feature_mask())
     return int(h.pgm_abi_features()) if hasattr(h, 'pgm_abi_features') else 0
 
 
@@ -245,6 +262,12 @@ def require_dst_device():
 def require_dummy_device():
     if not features() & FEATURE_DUMMY_DEVICE:
         raise PGMError('this libpgm.so has no MO-Dummy entry points or dim sets (pgm_abi_features() & 4 is clear); '
+                       'rebuild it with `python -m pgmorl_amd.build`')
+
+
+def require_any_dims():
+    if not features() & FEATURE_ANY_DIMS:
+        raise PGMError('this libpgm.so has no runtime-dim entry points (pgm_abi_feature_mask() & 8 is clear); '
                        'rebuild it with `python -m pgmorl_amd.build`')
 
 

@@ -164,6 +164,8 @@ int pgm_abi_version(void) { return PGM_ABI_VERSION; }
 int pgm_abi_minor(void) { return PGM_ABI_MINOR; }
 
 int pgm_abi_features(void) { return PGM_FEATURE_CATEGORICAL | PGM_FEATURE_DST_DEVICE | PGM_FEATURE_DUMMY_DEVICE; }
+// every group, the ones added after pgm_abi_features()'s value was frozen included
+int pgm_abi_feature_mask(void) { return pgm_abi_features() | PGM_FEATURE_ANY_DIMS; }
 
 int pgm_param_layout_cat(int32_t O, int32_t A, int32_t K, int32_t H, int32_t* offsets, int32_t* total) {
     if (O <= 0 || A <= 0 || K <= 0 || H <= 0 || !offsets || !total) {

@@ -99,10 +99,49 @@ def dummy_reset_table(seed, count, R=DUMMY_RESETS):
                      for i in range(count)])
 
 
+# Third-party envs (register_env): env id -> (obs_dim, act_dim or number of actions, obj_num, discrete).  Host-stepped
+# only (hostenv.GymHostVecEnv behind ``--host-env module:callable``), on the runtime-dim kernels (the *_any entry points
+# of include/pgm_abi.h), whose range these bounds restate.
+_USER_ENVS = {}
+USER_MAX_OBS, USER_MAX_ACT, USER_MAX_OBJ = 32, 8, 3
+
+
+def user_env_names():
+    return sorted(_USER_ENVS)
+
+
+def register_env(name, obs_dim, act_dim, obj_num, discrete=False):
+    """Make ``make_spec(name)`` know a third-party env: its dims with ``'user': True`` (and ``'discrete'``; act_dim is
+    then the number of actions).  ValueError for a name envspec already knows (a second registration with the same
+    dims is accepted) and for dims outside the runtime-dim kernels' range."""
+    O, A, K, disc = int(obs_dim), int(act_dim), int(obj_num), bool(discrete)
+    if name in _ENVS or name in _DISCRETE_ENVS or name in _NATIVE_ENVS:
+        raise ValueError(f'register_env: {name!r} is one of envspec\'s own envs')
+    if name in _USER_ENVS and _USER_ENVS[name] != (O, A, K, disc):
+        raise ValueError(f'register_env: {name!r} is already registered with (obs, act, obj, discrete) = '
+                         f'{_USER_ENVS[name]}')
+    if not 1 <= O <= USER_MAX_OBS:
+        raise ValueError(f'register_env: {name!r} has obs_dim {O}; the runtime-dim kernels take 1 <= obs_dim <= '
+                         f'{USER_MAX_OBS}')
+    if not (2 if disc else 1) <= A <= USER_MAX_ACT:
+        raise ValueError(f'register_env: {name!r} has {A} ' + ('actions' if disc else 'action dims') +
+                         f'; the runtime-dim kernels take {"2" if disc else "1"} <= it <= {USER_MAX_ACT}')
+    if not 1 <= K <= USER_MAX_OBJ:
+        raise ValueError(f'register_env: {name!r} has {K} objectives; the runtime-dim kernels take 1 <= obj_num <= '
+                         f'{USER_MAX_OBJ}')
+    _USER_ENVS[name] = (O, A, K, disc)
+
+
 def make_spec(env_name):
     """Constant arrays of one SynthMO env (all fp64); for a discrete-action env the dims alone, with
     ``discrete = True`` and ``act_dim`` the number of actions; for a native env the dims, ``bound``, the action clip
-    and ``native`` (no SynthMO arrays)."""
+    and ``native`` (no SynthMO arrays); for a registered third-party env the dims with ``user = True``."""
+    if env_name in _USER_ENVS:
+        O, A, K, disc = _USER_ENVS[env_name]
+        sp = {'name': env_name, 'obs_dim': O, 'act_dim': A, 'obj_num': K, 'user': True}
+        if disc:
+            sp['discrete'] = True
+        return sp
     if env_name in _NATIVE_ENVS:
         O, A, K, tmax, bound = _NATIVE_ENVS[env_name]
         return {'name': env_name, 'obs_dim': O, 'act_dim': A, 'obj_num': K, 'max_episode_steps': tmax, 'bound': bound,

@@ -73,6 +73,9 @@ class SynthHostVecEnv(HostVecEnv):
 
     def __init__(self, env_name, P, N, seed=0, max_episode_steps=None):
         sp = envspec.make_spec(env_name)
+        if sp.get('user'):
+            raise ValueError(f'{env_name} is a registered third-party env with no SynthMO stand-in (use --host-env '
+                             f'module:callable)')
         if sp.get('discrete'):
             raise ValueError(f'{env_name} has discrete actions and no SynthMO stand-in (use --host-env dst)')
         if sp.get('native'):
@@ -153,7 +156,7 @@ class DeepSeaTreasureHostVecEnv(HostVecEnv):
 
     def __init__(self, env_name='MO-DeepSeaTreasure-v0', P=1, N=1, seed=0, max_steps=None, time_limit_is_bad=False):
         sp = envspec.make_spec(env_name)
-        if not sp.get('discrete') or (sp['obs_dim'], sp['act_dim'], sp['obj_num']) != (3, 4, 2):
+        if sp.get('user') or not sp.get('discrete') or (sp['obs_dim'], sp['act_dim'], sp['obj_num']) != (3, 4, 2):
             raise ValueError(f'{env_name} is not a Deep Sea Treasure env (obs 3, 4 actions, 2 objectives)')
         self.env_name, self.seed = env_name, seed  # (the env draws nothing: every seed gives the same episodes)
         self.capacity = self.P = P
@@ -476,11 +479,44 @@ def resolve(spec):
     return lambda env_name, P, N, seed=0: GymHostVecEnv(fn, env_name, P, N, seed)
 
 
+def register_from_spec(spec, env_name, seed=0):
+    """For a ``module:callable`` spec and an env name envspec does not know: build one env, read its dims
+    (``probe_dims``, ``is_discrete``), register them (``envspec.register_env``: ValueError for dims outside the
+    runtime-dim kernels' range) and close the env.  Returns whether it registered; ``synth`` / ``dst`` / ``dummy`` and
+    names envspec knows are left alone, so an unknown name behind those still raises in ``check_spec``."""
+    if spec in ('synth', 'dst', 'dummy'):
+        return False
+    try:
+        envspec.make_spec(env_name)
+        return False
+    except ValueError:
+        pass
+    mod, sep, name = str(spec).partition(':')
+    if not sep or not mod or not name:
+        return False  # resolve() words the refusal
+    try:
+        fn = getattr(importlib.import_module(mod), name)
+    except (ImportError, AttributeError) as e:
+        raise ValueError(f'--host-env {spec!r}: cannot import ({e})') from e
+    env = fn(env_name, seed, 0)
+    try:
+        O, A, K = probe_dims(env)
+        disc = is_discrete(env.action_space)
+    finally:
+        if hasattr(env, 'close'):
+            env.close()
+    envspec.register_env(env_name, O, A, K, discrete=disc)
+    return True
+
+
 def check_spec(spec, env_name, seed=0):
     """Refuse, before anything is written or allocated, a --host-env whose env dims are not envspec's for env_name
     (the kernels are compiled for those dims).  Returns the factory."""
     factory = resolve(spec)
     want = envspec.make_spec(env_name)
+    if want.get('user') and spec in ('synth', 'dst', 'dummy'):
+        raise ValueError(f'--host-env {spec} cannot step the registered third-party env {env_name} (use --host-env '
+                         f'module:callable)')
     if spec == 'dummy' and want.get('native') != 'dummy':
         raise ValueError(f'--host-env dummy steps the MO-Dummy envs only ({envspec.native_env_names()}), not {env_name}')
     want = (want['obs_dim'], want['act_dim'], want['obj_num'])

@@ -102,6 +102,22 @@ def main(argv=None):
     argv = sys.argv[1:] if argv is None else argv
     torch.set_default_dtype(torch.float64)
     args = get_parser().parse_args(merge_argv(argv))
+    if args.host_env is not None and ':' in str(args.host_env):
+        # an env name envspec does not know behind --host-env module:callable: a third-party env, registered with the
+        # dims of one probe env (the runtime-dim kernels); dims out of their range and --layernorm are refused here
+        from ._lib import PGMError
+        from . import envspec
+        from .hostenv import register_from_spec
+        try:
+            register_from_spec(args.host_env, args.env_name, args.seed)
+        except ValueError as e:
+            raise PGMError(str(e)) from e
+        if args.env_name in envspec.user_env_names():
+            if args.layernorm:
+                raise PGMError(f'--layernorm with {args.env_name}: a third-party env runs on the runtime-dim kernels, '
+                               f'which are built for plain towers only')
+            if args.device_env:
+                raise PGMError(f'--device-env with {args.env_name}: a third-party env is host-stepped only')
     if args.layernorm:  # refused here, before the save dir or the device is touched
         from ._lib import PGMError
         from .envspec import make_spec

@@ -29,8 +29,9 @@ import numpy as np
 import torch
 
 from . import envspec
-from ._lib import (Dims, DstSpec, DummySpec, EnvSpec, EnvState, NormState, PGMError, PPOHParams, RolloutBuf, check,
-                   launch_opts, lib, require_categorical, require_dst_device, require_dummy_device)
+from ._lib import (ANY_MAX_ACT, ANY_MAX_OBJ, ANY_MAX_OBS, Dims, DstSpec, DummySpec, EnvSpec, EnvState, NormState,
+                   PGMError, PPOHParams, RolloutBuf, check, launch_opts, lib, require_any_dims, require_categorical,
+                   require_dst_device, require_dummy_device)
 from .layout import ParamLayout
 
 F32, F64, I32 = torch.float32, torch.float64, torch.int32
@@ -67,7 +68,7 @@ class TaskBatch:
                  clip_param=0.2, ppo_epoch=10, num_mini_batch=32, value_loss_coef=0.5, entropy_coef=0.0,
                  max_grad_norm=0.5, adam_eps=1e-5, use_clipped_value_loss=True, device='cuda', capacity=None,
                  layernorm=False, host_env=None, device_env=False, *, max_steps=None, time_limit_is_bad=None,
-                 bound=None, R=None):
+                 bound=None, R=None, any_dims=False):
         """device_env: run a discrete-action env on the device (Deep Sea Treasure: pgm_rollout_dst / pgm_eval_dst)
         instead of on the host; for such an env exactly one of host_env and device_env=True is given.  The SynthMO envs
         are device envs already: the flag changes nothing there.  max_steps / time_limit_is_bad: the device Deep Sea
@@ -75,7 +76,9 @@ class TaskBatch:
         hostenv.DeepSeaTreasureHostVecEnv has them.  An MO-Dummy env is a device env by default (device_env changes
         nothing); max_steps (default 500), bound (5.0), time_limit_is_bad (here default True: the registration's
         TimeLimitMask) and R (reset positions per env, default envspec.DUMMY_RESETS) are the device env's, as
-        hostenv.DummyMOHostVecEnv has them."""
+        hostenv.DummyMOHostVecEnv has them.  any_dims=True: run a host-stepped batch of an env envspec knows on the
+        runtime-dim kernels (the *_any entry points) instead of the ones compiled for its dims; a registered
+        third-party env (envspec.register_env) always runs on them."""
         self.spec = envspec.make_spec(env_name)
         sp = self.spec
         self.host_env = host_env
@@ -90,6 +93,25 @@ class TaskBatch:
         self.ppo_epoch, self.num_mini_batch = ppo_epoch, num_mini_batch
         self.dev = torch.device(device)
         self.layernorm = bool(layernorm)
+        # the runtime-dim kernel family: host-stepped, plain towers, at most ANY_EVAL_MAX evaluation episodes
+        self.any_dims = bool(sp.get('user')) or bool(any_dims)
+        if self.any_dims:
+            what = f'{env_name} runs on the runtime-dim kernels (a registered third-party env, or any_dims=True)'
+            if device_env:
+                raise PGMError(f'device_env=True: {what}, which step no env on the device; give host_env=...')
+            if host_env is None:
+                raise PGMError(f'{what}, which are host-stepped only: TaskBatch needs host_env=... '
+                               f'(hostenv.GymHostVecEnv, --host-env module:callable)')
+            if self.layernorm:
+                raise PGMError(f'layernorm=True: {what}, which are built for plain towers only')
+            if eval_num > self.HOST_EVAL_MAX:
+                raise PGMError(f'eval_num={eval_num}: {what}, which evaluate at most {self.HOST_EVAL_MAX} episodes '
+                               f'per task')
+            amin = 2 if sp.get('discrete') else 1
+            if not (1 <= self.O <= ANY_MAX_OBS and amin <= self.A <= ANY_MAX_ACT and 1 <= self.K <= ANY_MAX_OBJ):
+                raise PGMError(f'{what}, which take obs_dim <= {ANY_MAX_OBS}, {amin} <= act_dim <= {ANY_MAX_ACT} and '
+                               f'obj_num <= {ANY_MAX_OBJ}; {env_name} has {(self.O, self.A, self.K)}')
+            require_any_dims()
         if self.layernorm and self.O > LN_MAX_OBS:
             raise PGMError(f'layernorm=True with {env_name}: the LayerNorm kernels keep layer 1 LDS-resident and are '
                            f'built for obs_dim <= {LN_MAX_OBS}; obs_dim {self.O} would need a streamed layer-1 '
@@ -199,6 +221,8 @@ class TaskBatch:
         self._eval_stream, self._eval_done = None, None
         self._reset_pending = False  # a pgm_ppo_update_reset queued on the side stream, not yet waited for
         ws_bytes = lib().pgm_ppo_update_cat_workspace_bytes if self.discrete else lib().pgm_ppo_update_workspace_bytes
+        if self.any_dims:
+            ws_bytes = lib().pgm_ppo_update_any_workspace_bytes
         nws = ws_bytes(C.byref(Dims(Pc, N, T, O, A, K, self.H, int(self.layernorm))))
         self.update_ws = torch.zeros((nws + 7) // 8, dtype=torch.int64, device=self.dev)
         # sticky OR of every update's exchange-timeout word (workspace word 2P, include/pgm_abi.h): a launch
@@ -275,6 +299,11 @@ class TaskBatch:
         self._tr_ready = torch.cuda.Event()
         self._tr_ready.record()
         do, dj, dr, dd, db = self._d_seg
+        if self.any_dims:
+            check(lib().pgm_env_ingest_any(C.byref(self.dims), C.byref(self.c_state), C.byref(self.c_norm),
+                                           C.byref(self.c_rb), t, _ptr(do), _ptr(dj), _ptr(dr), _ptr(dd), _ptr(db),
+                                           _stream()), 'pgm_env_ingest_any')
+            return
         check(lib().pgm_env_ingest(C.byref(self.dims), C.byref(self.c_state), C.byref(self.c_norm),
                                    C.byref(self.c_rb), t, _ptr(do), _ptr(dj), _ptr(dr), _ptr(dd), _ptr(db),
                                    _stream()), 'pgm_env_ingest')
@@ -286,6 +315,11 @@ class TaskBatch:
         check(fn(self.noise.numel(), C.c_uint64(seed), _ptr(self.noise), _stream()), what)
 
     def _rollout_act(self, t):
+        if self.any_dims:
+            check(lib().pgm_rollout_act_any(C.byref(self.dims), int(self.discrete), _ptr(self.params),
+                                            C.byref(self.c_rb), t, _ptr(self.noise), _ptr(self._d_act), _stream()),
+                  'pgm_rollout_act_any')
+            return
         if self.discrete:
             check(lib().pgm_rollout_act_cat(C.byref(self.dims), _ptr(self.params), C.byref(self.c_rb), t,
                                             _ptr(self.noise), _ptr(self._d_act), _stream()), 'pgm_rollout_act_cat')
@@ -347,6 +381,11 @@ class TaskBatch:
         alive = np.ones((P, E), dtype=bool)
         obs = he.eval_reset(E)
         d = Dims(P, 1, 0, O, self.A, K, self.H, int(self.layernorm))
+        if self.any_dims:
+            any_fn, head, what = lib().pgm_eval_act_any, int(self.discrete), 'pgm_eval_act_any'
+
+            def eval_act(d_, *rest):
+                return any_fn(d_, head, *rest)
         while alive.any():
             obs_np[...] = obs
             self._d_eobs[:P * E * O].copy_(h_obs, non_blocking=True)
@@ -419,7 +458,7 @@ class TaskBatch:
         st = self._spec_t
         # (a discrete-action env has no SynthMO constants: NULL pointers, and no entry point that reads them is called)
         self.c_spec = EnvSpec(*(_ptr(st.get(k)) for k in ('d', 'U', 'c', 'V', 'ebase', 'ecoef', 'act_lo', 'act_hi')),
-                              self.spec['max_episode_steps'], 0)
+                              self.spec.get('max_episode_steps', 0), 0)
         self.c_state = EnvState(_ptr(self.s), _ptr(self.elapsed), _ptr(self.obj_acc), _ptr(self.obj_valid),
                                 _ptr(self.ret), _ptr(self.s0_train))
         self.c_norm = NormState(_ptr(self.ob_mean), _ptr(self.ob_var), _ptr(self.ob_count), _ptr(self.ret_mean),
@@ -472,6 +511,9 @@ class TaskBatch:
         return out
 
     def env_step(self, action):
+        if self.any_dims:
+            raise PGMError('env_step: this batch runs on the runtime-dim kernels, which are host-stepped only: the '
+                           'environments are stepped inside rollout(), there is no device env to step')
         if self.host_env is not None:
             raise PGMError('env_step: this batch is in host-env mode (TaskBatch(host_env=...)): the environments are '
                            'stepped on the host inside rollout(), there is no device env to step')
@@ -492,6 +534,9 @@ class TaskBatch:
         return obs, rew, m, b
 
     def act(self, obs, noise=None, deterministic=False):
+        if self.any_dims:
+            raise PGMError('act: the runtime-dim kernels have no stand-alone Policy.act (pgm_act_forward is compiled '
+                           'per dim set); pgm_rollout_act_any acts on the rollout storage inside rollout()')
         P, N = self.P, obs.shape[1]
         obs = obs.to(device=self.dev, dtype=F32).contiguous()
         d = Dims(P, N, self.T, self.O, self.A, self.K, self.H, int(self.layernorm))
@@ -563,6 +608,12 @@ class TaskBatch:
     def ppo_update_launch(self):
         """pgm_ppo_update alone (packed rows + the update kernel) on the current stream; discrete actions:
         pgm_ppo_update_cat (it gathers from the storage itself: no packed rows)."""
+        if self.any_dims:
+            check(lib().pgm_ppo_update_any(C.byref(self.dims), int(self.discrete), C.byref(self.hp), _ptr(self.params),
+                                           _ptr(self.adam_m), _ptr(self.adam_v), _ptr(self.adam_step), _ptr(self.lr),
+                                           _ptr(self.perms), C.byref(self.c_rb), _ptr(self.stats),
+                                           _ptr(self.update_ws), _stream()), 'pgm_ppo_update_any')
+            return
         if self.discrete:
             check(lib().pgm_ppo_update_cat(C.byref(self.dims), C.byref(self.hp), _ptr(self.params), _ptr(self.adam_m),
                                            _ptr(self.adam_v), _ptr(self.adam_step), _ptr(self.lr), _ptr(self.perms),
@@ -576,6 +627,8 @@ class TaskBatch:
 
     def update_variant(self):
         """The update kernel pgm_ppo_update launches for this batch (pgm_ppo_update_variant: the launcher's own rule)."""
+        if self.any_dims:
+            return 'ppo_update_any_kernel'
         if self.discrete:  # one kernel, no launch choice
             return 'ppo_update_cat_kernel (one workgroup per tower)'
         buf = C.create_string_buffer(128)
@@ -697,7 +750,7 @@ class TaskBatch:
             # the timeout word of this update, folded off the main stream, then the next update's workspace reset
             # (the next update waits for this stream: perm_ready)
             self.fold_update_flag()
-            if not self.discrete:  # (pgm_ppo_update_cat resets its own, smaller workspace inside the call:
+            if not self.discrete and not self.any_dims:  # (pgm_ppo_update_cat / _any reset their own, smaller workspace:
                 # pgm_ppo_update_reset clears the exchange slots of pgm_ppo_update's layout, which it does not have)
                 check(lib().pgm_ppo_update_reset(C.byref(self.dims), _ptr(self.update_ws), _stream()),
                       'pgm_ppo_update_reset')

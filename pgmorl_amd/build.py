@@ -1,5 +1,7 @@
 """Build libpgm.so (gfx950) with hipcc and libpgm_host.so with g++, in-tree.  ``python -m pgmorl_amd.build``."""
+import hashlib
 import os
+import re
 import subprocess
 import sys
 from concurrent.futures import ThreadPoolExecutor
@@ -117,6 +119,86 @@ def _build_test(force=False, verbose=False):
         if r.returncode != 0:
             raise RuntimeError(f'hipcc link failed (test build):\n{r.stdout}\n{r.stderr}')
     return TEST_LIB
+
+
+# ---- device env plug-ins (include/pgm_envplug.h): one library per user env header
+ENV_DIR = os.path.join(HERE, 'build_env')
+ENV_SOURCE = 'pgm_envplug.hip'
+ENV_HEADERS = ['pgm_envplug.hpp', 'pgm_policy_dev.hpp', 'pgm_dispatch.hpp', 'pgm_rollout.hpp', 'pgm_common.hpp']
+ENV_MAX_JOBS = 4  # compile processes of one build_envs batch, as build() (never sized from the CPU count)
+_QUOTED_INCLUDE = re.compile(r'^[ \t]*#[ \t]*include[ \t]*"([^"]+)"', re.M)
+
+
+def _env_header_closure(header):
+    """The header and the files it includes with quotes (resolved beside the including file, then in include/)."""
+    seen, todo = [], [os.path.abspath(header)]
+    while todo:
+        f = todo.pop()
+        if f in seen:
+            continue
+        seen.append(f)
+        with open(f, 'r', errors='replace') as fh:
+            text = fh.read()
+        for inc in _QUOTED_INCLUDE.findall(text):
+            for base in (os.path.dirname(f), os.path.join(ROOT, 'include')):
+                cand = os.path.normpath(os.path.join(base, inc))
+                if os.path.isfile(cand):
+                    todo.append(cand)
+                    break
+    return seen
+
+
+def env_lib_path(header, stamps=False):
+    """build_env/<stem>-<first 12 hex of sha256(the header, what it includes, pgm_envplug.hip and the csrc / include
+    headers that includes)>/libpgm_env.so: a changed header is a new library."""
+    h = hashlib.sha256()
+    files = _env_header_closure(header) + [os.path.join(CSRC, ENV_SOURCE)] + [os.path.join(CSRC, x) for x in ENV_HEADERS]
+    files += [os.path.join(ROOT, 'include', x) for x in ('pgm_envplug.h', 'pgm_abi.h')]
+    for f in files:
+        with open(f, 'rb') as fh:
+            h.update(fh.read())
+        h.update(b'\0')
+    h.update(' '.join(FLAGS[:3] + [ARCH]).encode())
+    stem = os.path.splitext(os.path.basename(header))[0]
+    return os.path.join(ENV_DIR, f'{stem}-{h.hexdigest()[:12]}' + ('-stamps' if stamps else ''), 'libpgm_env.so')
+
+
+def build_env(header, force=False, verbose=False, stamps=False):
+    """Compile csrc/pgm_envplug.hip with the user env header force-included (build.FLAGS) into a plug-in library of
+    its own; returns its path.  Rebuilds only when the hash of env_lib_path changes.  RuntimeError with the compiler's
+    output (the static_assert naming a missing member or a broken limit) when the header does not build.
+    stamps=True builds the diagnostic form beside it (-DPGM_STAMPS phase timers, pgm_debug_stamps_envplug); never the
+    library a run loads."""
+    header = os.path.abspath(header)
+    if not os.path.isfile(header):
+        raise RuntimeError(f'build_env: no env header at {header}')
+    lib = env_lib_path(header, stamps)
+    if not force and os.path.exists(lib):
+        return lib
+    os.makedirs(os.path.dirname(lib), exist_ok=True)
+    tmp = f'{lib}.{os.getpid()}.tmp'
+    cmd = [_hipcc(), *FLAGS, *(['-DPGM_STAMPS'] if stamps else []), '-I', os.path.dirname(header), '-include', header, '-shared', '-Wl,-Bsymbolic',
+           os.path.join(CSRC, ENV_SOURCE), '-o', tmp]
+    if verbose:
+        print(' '.join(cmd), flush=True)
+    r = subprocess.run(cmd, capture_output=True, text=True)
+    if r.returncode != 0:
+        if os.path.exists(tmp):
+            os.remove(tmp)
+        if not os.listdir(os.path.dirname(lib)):  # no empty directory behind a header that does not build
+            os.rmdir(os.path.dirname(lib))
+        raise RuntimeError(f'hipcc failed on the env plug-in {header}:\n{r.stdout}\n{r.stderr}')
+    os.replace(tmp, lib)
+    return lib
+
+
+def build_envs(headers, force=False, verbose=False):
+    """build_env for several headers, at most ENV_MAX_JOBS compile processes at a time."""
+    headers = list(headers)
+    if not headers:
+        return []
+    with ThreadPoolExecutor(max_workers=min(ENV_MAX_JOBS, len(headers))) as ex:
+        return list(ex.map(lambda h: build_env(h, force=force, verbose=verbose), headers))
 
 
 if __name__ == '__main__':

@@ -99,6 +99,21 @@ def dummy_reset_table(seed, count, R=DUMMY_RESETS):
                      for i in range(count)])
 
 
+PLUGIN_RESET_STREAM = 0xE9F10000  # the splitmix64 stream constant of the env plug-ins' reset uniforms
+
+
+def plugin_reset_table(seed, count, R, RW):
+    """[count][R][RW] fp64 uniforms in [0, 1) for the reset function of a device env plug-in (include/pgm_envplug.h):
+    row i holds the splitmix64 uniforms of env seed ``seed + i`` (dummy_reset_table's construction without the
+    2 u - 1).  Training env n of every task starts its episode e at entry (n, e mod R); evaluation episode e starts at
+    entry (e, 0) of the table of eval_num rows."""
+    if R < 1:
+        raise ValueError(f'plugin_reset_table: R = {R} reset entries per env must be at least 1')
+    if RW < 0:
+        raise ValueError(f'plugin_reset_table: RW = {RW} uniforms per entry must not be negative')
+    return np.stack([_uniforms(PLUGIN_RESET_STREAM + int(seed) + i, R * RW).reshape(R, RW) for i in range(count)])
+
+
 # Third-party envs (register_env): env id -> (obs_dim, act_dim or number of actions, obj_num, discrete).  Host-stepped
 # only (hostenv.GymHostVecEnv behind ``--host-env module:callable``), on the runtime-dim kernels (the *_any entry points
 # of include/pgm_abi.h), whose range these bounds restate.

@@ -11,6 +11,8 @@ fp64 observations, the scalar env reward, ``info['obj']`` and the done / bad_tra
                        shipped run, vectorised numpy.
 * ``DummyMOHostVecEnv``  MO-Dummy-v0 / MO-Dummy3-v0 (``--host-env dummy``), the reference's MuJoCo-free continuous env,
                        vectorised numpy with the device env's operation order.
+* ``PluginHostVecEnv``  a device env plug-in (envplug.EnvPlugin, ``--env-plugin HEADER --host-env plugin``) stepped on
+                       the host by the plug-in library's own host functions: the same compiled header on the CPU.
 * ``GymHostVecEnv``    any ``make_env(env_name, seed, rank)`` returning gym-style objects (duck-typed: gym itself is
                        never imported here), in the 4-tuple or the 5-tuple step API.
 """
@@ -328,6 +330,83 @@ class DummyMOHostVecEnv(HostVecEnv):
         obj, _, done, _ = self._move(self._est, actions, frozen=self._edone)  # ended episodes stand still
         self._edone = self._edone | done
         return self._est['s'].copy(), obj, self._edone.copy()
+
+
+class PluginHostVecEnv(HostVecEnv):
+    """A device env plug-in (envplug.EnvPlugin) stepped on the host: ``step``, ``eval_step`` and the resets call the
+    plug-in library's pgm_envplug_transition / pgm_envplug_reset, i.e. the compiled header's own functions with the
+    forced step limit and the auto-reset.  The reference point of the fused path (for a header without transcendentals
+    the two agree bit for bit) and a debugging path for the header's author.  Env n of every task uses row n of
+    envspec.plugin_reset_table(seed, N, R, RW); evaluation episode e starts at entry (e, 0) of the eval_num-row
+    table."""
+
+    def __init__(self, plugin, P, N, seed=0, R=None):
+        from . import envplug
+        self.plugin = pl = envplug.as_plugin(plugin)
+        self.seed = seed
+        self.capacity = self.P = P
+        self.N = N
+        self.obs_dim, self.act_dim, self.obj_num = pl.O, pl.A, pl.K
+        self.discrete = pl.DISCRETE
+        self.R = int(envplug.DEFAULT_RESETS if R is None else R)
+        self.table = envspec.plugin_reset_table(seed, N, self.R, pl.RW)
+        self._st = self._est = self._etable = self._edone = None
+
+    def set_active(self, P):
+        if not 0 < P <= self.capacity:
+            raise ValueError(f'active tasks {P} outside [1, {self.capacity}]')
+        self.P = P
+        self._st = None
+
+    def _fresh(self, P, M, table):
+        row = np.broadcast_to(np.arange(M, dtype=np.int32), (P, M)).reshape(-1).copy()
+        zero = np.zeros(P * M, dtype=np.int32)
+        sd, si, obs = self.plugin.reset(row, zero, table)
+        return {'sd': sd, 'si': si, 'elapsed': zero.copy(), 'episode': zero.copy(), 'row': row}, obs
+
+    def _action(self, actions):
+        if self.discrete:
+            return np.asarray(actions).astype(np.int32).reshape(-1)
+        return np.asarray(actions, dtype=np.float32).reshape(-1, self.act_dim)
+
+    def reset(self):
+        self._st, obs = self._fresh(self.P, self.N, self.table)
+        return obs.reshape(self.P, self.N, self.obs_dim)
+
+    def step(self, actions):
+        st, P, N = self._st, self.P, self.N
+        o = self.plugin.transition(st['sd'], st['si'], st['elapsed'], st['episode'], st['row'],
+                                   self._action(actions), self.table)
+        for k in ('sd', 'si', 'elapsed', 'episode'):
+            st[k] = o[k]
+        return (o['obs'].reshape(P, N, self.obs_dim), o['reward'].reshape(P, N), o['done'].reshape(P, N).astype(bool),
+                o['bad'].reshape(P, N).astype(bool), o['obj'].reshape(P, N, self.obj_num))
+
+    def eval_reset(self, eval_num):
+        self._etable = envspec.plugin_reset_table(self.seed, eval_num, self.R, self.plugin.RW)
+        self._est, obs = self._fresh(self.P, eval_num, self._etable)
+        self._edone = np.zeros(self.P * eval_num, dtype=bool)
+        self._eobs = obs
+        return obs.reshape(self.P, eval_num, self.obs_dim).copy()
+
+    def eval_step(self, actions):
+        st, P = self._est, self.P
+        E = self._edone.size // P
+        act = self._action(actions)
+        if self.discrete:  # an ended episode's action is not looked at (and may be anything)
+            act = np.where(self._edone, 0, act).astype(np.int32)
+        o = self.plugin.transition(st['sd'], st['si'], st['elapsed'], st['episode'], st['row'], act, self._etable)
+        live = ~self._edone  # ended episodes stand still
+        for k in ('sd', 'si', 'elapsed', 'episode'):
+            m = live.reshape((-1,) + (1,) * (o[k].ndim - 1))
+            st[k] = np.where(m, o[k], st[k])
+        done = o['done'].astype(bool) & live
+        # (a done episode has been auto-reset by the transition; it is never stepped again, its state is not read)
+        self._eobs = np.where((live & ~done)[:, None], o['obs'], self._eobs)
+        obj = np.where(live[:, None], o['obj'], 0.0)
+        self._edone = self._edone | done
+        return (self._eobs.reshape(P, E, self.obs_dim).copy(), obj.reshape(P, E, self.obj_num),
+                self._edone.reshape(P, E).copy())
 
 
 def _reset_obs(r):

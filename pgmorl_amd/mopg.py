@@ -48,17 +48,32 @@ def linear_lr(j, total_num_updates, lr, ratio=1.0):
 
 
 class MOPGPopulation:
-    def __init__(self, args, device='cuda', rng='device', host_env=None, device_env=None):
+    def __init__(self, args, device='cuda', rng='device', host_env=None, device_env=None, env_plugin=None):
         """host_env (default ``args.host_env``, the --host-env flag; None = the device envs): 'synth',
         'module:callable' or a factory (env_name, P, N, seed) -> hostenv.HostVecEnv.  The environments then run on
         the host and every TaskBatch of this runtime is built over a HostVecEnv of its own task slots (a rank holds
         host envs for its block of the population only).  device_env (default ``args.device_env``, the --device-env
-        flag): a discrete-action env runs on the device (TaskBatch(device_env=True)); a no-op on the SynthMO envs."""
+        flag): a discrete-action env runs on the device (TaskBatch(device_env=True)); a no-op on the SynthMO envs.
+        env_plugin (default ``args.env_plugin``, the --env-plugin flag): an envplug.EnvPlugin or the path of its header;
+        every TaskBatch of this runtime runs the plug-in's fused kernels (the library is loaded once and reused when the
+        batch is re-allocated at a larger capacity), or, with host_env 'plugin', steps the same header on the host."""
         self.args = args
         self.device = torch.device(device)
         self.rng = rng
         self.tb = None
         host_env = getattr(args, 'host_env', None) if host_env is None else host_env
+        env_plugin = getattr(args, 'env_plugin', None) if env_plugin is None else env_plugin
+        self.env_plugin = None
+        if env_plugin is not None:
+            from .envplug import as_plugin
+            self.env_plugin = as_plugin(env_plugin)
+            self.env_plugin.register(args.env_name)
+        if host_env == 'plugin':
+            if self.env_plugin is None:
+                raise ValueError('host_env "plugin" steps an env plug-in on the host: give env_plugin=...')
+            from .hostenv import PluginHostVecEnv
+            plugin = self.env_plugin
+            host_env = lambda env_name, P, N, seed=0: PluginHostVecEnv(plugin, P, N, seed)  # noqa: E731
         if isinstance(host_env, str):
             from .hostenv import resolve
             host_env = resolve(host_env)
@@ -98,7 +113,8 @@ class MOPGPopulation:
                                 num_mini_batch=a.num_mini_batch, value_loss_coef=a.value_loss_coef,
                                 entropy_coef=a.entropy_coef, max_grad_norm=a.max_grad_norm, device=self.device,
                                 capacity=cap, layernorm=bool(getattr(a, 'layernorm', False)), host_env=he,
-                                device_env=self.device_env)
+                                device_env=self.device_env,
+                                env_plugin=self.env_plugin if he is None else None)
         else:
             self.tb.set_active(P)
         return self.tb

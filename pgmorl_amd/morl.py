@@ -55,17 +55,20 @@ def initialize_warm_up_batch(args, runtime):
     return samples, scal
 
 
-def run(args, device='cuda', rng='device', log=print, runtime=None, host_env=None, device_env=None):
+def run(args, device='cuda', rng='device', log=print, runtime=None, host_env=None, device_env=None,
+        env_plugin=None):
     """The generation loop.  ``runtime`` (default: MOPGPopulation on ``device``) is the MOPG back end: any
     object with MOPGPopulation's run / evaluate_samples / materialize / _batch(P).layout / device.
     ``log=None`` silences the progress lines (and skips formatting them).
     ``host_env`` (default: ``args.host_env``, i.e. --host-env): 'synth', 'module:callable' or a factory
     (env_name, P, N, seed) -> hostenv.HostVecEnv; the environments then run on the host (MOPGPopulation).
-    ``device_env`` (default: ``args.device_env``, i.e. --device-env): a discrete-action env runs on the device."""
+    ``device_env`` (default: ``args.device_env``, i.e. --device-env): a discrete-action env runs on the device.
+    ``env_plugin`` (default: ``args.env_plugin``, i.e. --env-plugin): an envplug.EnvPlugin or the path of its header."""
     np.random.seed(args.seed)
     torch.manual_seed(args.seed)
     t_start = time.perf_counter()
-    runtime = (MOPGPopulation(args, device=device, rng=rng, host_env=host_env, device_env=device_env)
+    runtime = (MOPGPopulation(args, device=device, rng=rng, host_env=host_env, device_env=device_env,
+                              env_plugin=env_plugin)
                if runtime is None else runtime)
     template = WeightedSumScalarization(num_objs=args.obj_num, weights=np.ones(args.obj_num) / args.obj_num)
     total_num_updates = int(args.num_env_steps) // args.num_steps // args.num_processes

@@ -4,7 +4,8 @@
 
 Adds ``--rng {device,host}`` (device counter streams, or the reference's own torch draws for
 bit-compatible runs), ``--device``, ``--host-env SPEC`` (environments stepped on the host, hostenv.py) and
-``--device-env`` (a discrete-action env, Deep Sea Treasure, stepped on the device instead).
+``--device-env`` (a discrete-action env, Deep Sea Treasure, stepped on the device instead) and ``--env-plugin HEADER``
+(a user env stated as a C++ header, include/pgm_envplug.h, compiled into fused rollout and evaluation kernels).
 """
 import argparse
 import os
@@ -69,6 +70,10 @@ def get_parser():
     add('--device-env', action='store_true', default=False,
         help='run a discrete-action env on the device (MO-DeepSeaTreasure-v0: the fused Categorical rollout and '
              'evaluation) instead of --host-env; no effect on the SynthMO envs, which are device envs already')
+    add('--env-plugin', default=None, metavar='HEADER',
+        help='train on a user env stated as one C++ header (include/pgm_envplug.h): the header is compiled into a '
+             'fused rollout and evaluation kernel of its own; --env-name is then any name envspec does not know.  '
+             'With "--host-env plugin" the same compiled header is stepped on the host instead')
     return ap
 
 
@@ -102,7 +107,28 @@ def main(argv=None):
     argv = sys.argv[1:] if argv is None else argv
     torch.set_default_dtype(torch.float64)
     args = get_parser().parse_args(merge_argv(argv))
-    if args.host_env is not None and ':' in str(args.host_env):
+    if args.env_plugin is not None or args.host_env == 'plugin':
+        # every refusal of a plug-in run, before the save dir or the device is touched; then the env name is registered
+        # with the header's dims and the loaded library travels in args.env_plugin
+        from ._lib import PGMError
+        if args.env_plugin is None:
+            raise PGMError('--host-env plugin steps the header of --env-plugin HEADER on the host: pass --env-plugin')
+        if args.layernorm:
+            raise PGMError('--layernorm with --env-plugin: env plug-ins are built for plain towers only')
+        if args.device_env:
+            raise PGMError('--device-env with --env-plugin: the plug-in\'s fused kernels already step the env on the '
+                           'device; --device-env selects the built-in Deep Sea Treasure')
+        if args.host_env not in (None, 'plugin'):
+            raise PGMError(f'--host-env {args.host_env} with --env-plugin: the one host env of a plug-in run is '
+                           f'"--host-env plugin" (the same header stepped on the host)')
+        from .envplug import EnvPlugin
+        plugin = EnvPlugin(args.env_plugin)  # PGMError with the compiler's message when the header does not build
+        try:
+            plugin.register(args.env_name)
+        except ValueError as e:
+            raise PGMError(f'--env-plugin with --env-name {args.env_name}: {e}') from e
+        args.env_plugin = plugin
+    elif args.host_env is not None and ':' in str(args.host_env):
         # an env name envspec does not know behind --host-env module:callable: a third-party env, registered with the
         # dims of one probe env (the runtime-dim kernels); dims out of their range and --layernorm are refused here
         from ._lib import PGMError
@@ -140,7 +166,8 @@ def main(argv=None):
                            f'Sea Treasure inside the fused rollout kernel)')
         if args.layernorm:
             raise PGMError(f'--layernorm with {args.env_name}: LayerNorm towers with a Categorical head are not built')
-    if args.host_env is not None:  # refused here too: a spec that cannot be imported or whose env dims differ
+    if args.host_env is not None and args.host_env != 'plugin':  # refused here too: a spec that cannot be imported
+        # or whose env dims differ
         from ._lib import PGMError
         from .hostenv import check_spec
         try:

@@ -21,6 +21,10 @@ Categorical head and the grid world stepped inside the kernels.
 The MO-Dummy envs (envspec.native_env_names(): the reference's MuJoCo-free continuous env) are device envs by default,
 like SynthMO: the rollout is pgm_rollout_dummy, the evaluation pgm_eval_dummy, everything else the Gaussian kernels.
 ``host_env=hostenv.DummyMOHostVecEnv(...)`` selects the host-stepped path instead.
+
+With ``env_plugin`` (an ``envplug.EnvPlugin`` or the path of a user env header, include/pgm_envplug.h) the env is the
+user's own: the rollout is pgm_envplug_rollout and the evaluation pgm_envplug_eval of the plug-in's library, one launch
+each, and returns, advantages and the PPO update are the runtime-dim kernels of libpgm.so on the same storage.
 """
 import ctypes as C
 import math
@@ -68,7 +72,7 @@ class TaskBatch:
                  clip_param=0.2, ppo_epoch=10, num_mini_batch=32, value_loss_coef=0.5, entropy_coef=0.0,
                  max_grad_norm=0.5, adam_eps=1e-5, use_clipped_value_loss=True, device='cuda', capacity=None,
                  layernorm=False, host_env=None, device_env=False, *, max_steps=None, time_limit_is_bad=None,
-                 bound=None, R=None, any_dims=False):
+                 bound=None, R=None, any_dims=False, env_plugin=None):
         """device_env: run a discrete-action env on the device (Deep Sea Treasure: pgm_rollout_dst / pgm_eval_dst)
         instead of on the host; for such an env exactly one of host_env and device_env=True is given.  The SynthMO envs
         are device envs already: the flag changes nothing there.  max_steps / time_limit_is_bad: the device Deep Sea
@@ -78,7 +82,29 @@ class TaskBatch:
         TimeLimitMask) and R (reset positions per env, default envspec.DUMMY_RESETS) are the device env's, as
         hostenv.DummyMOHostVecEnv has them.  any_dims=True: run a host-stepped batch of an env envspec knows on the
         runtime-dim kernels (the *_any entry points) instead of the ones compiled for its dims; a registered
-        third-party env (envspec.register_env) always runs on them."""
+        third-party env (envspec.register_env) always runs on them.  env_plugin: a device env plug-in
+        (envplug.EnvPlugin, or the path of its header): env_name is registered with the header's dims, the batch is a
+        runtime-dim batch whose rollout and evaluation are the plug-in library's fused kernels, on the device envs'
+        schedule (overlapped evaluation included); R: reset-table entries per env (default envplug.DEFAULT_RESETS)."""
+        self.plugin = None
+        if env_plugin is not None:
+            from . import envplug
+            if host_env is not None or device_env:
+                raise PGMError('env_plugin=... steps the env inside the plug-in\'s fused kernels: host_env=... and '
+                               'device_env=True are other places to step it; give env_plugin alone (the same header on '
+                               'the host: host_env=hostenv.PluginHostVecEnv(plugin, ...) without env_plugin)')
+            if layernorm:
+                raise PGMError('layernorm=True with env_plugin=...: env plug-ins are built for plain towers only')
+            if eval_num > self.HOST_EVAL_MAX or eval_num < 1:
+                raise PGMError(f'eval_num={eval_num} with env_plugin=...: a plug-in evaluates 1..{self.HOST_EVAL_MAX} '
+                               f'episodes per task in one launch')
+            if num_processes > 8:
+                raise PGMError(f'num_processes={num_processes} with env_plugin=...: envs per task > 8 unsupported')
+            self.plugin = envplug.as_plugin(env_plugin)
+            try:
+                self.plugin.register(env_name)
+            except ValueError as e:
+                raise PGMError(f'env_plugin=...: {e}') from e
         self.spec = envspec.make_spec(env_name)
         sp = self.spec
         self.host_env = host_env
@@ -99,7 +125,7 @@ class TaskBatch:
             what = f'{env_name} runs on the runtime-dim kernels (a registered third-party env, or any_dims=True)'
             if device_env:
                 raise PGMError(f'device_env=True: {what}, which step no env on the device; give host_env=...')
-            if host_env is None:
+            if host_env is None and self.plugin is None:
                 raise PGMError(f'{what}, which are host-stepped only: TaskBatch needs host_env=... '
                                f'(hostenv.GymHostVecEnv, --host-env module:callable)')
             if self.layernorm:
@@ -121,7 +147,7 @@ class TaskBatch:
         self.discrete = bool(sp.get('discrete', False))
         self.device_env = bool(device_env) and self.discrete  # (a SynthMO env is a device env with or without the flag)
         if self.discrete:
-            if host_env is None and not device_env:
+            if host_env is None and not device_env and self.plugin is None:
                 raise PGMError(f'{env_name} has discrete actions and no default device environment: TaskBatch needs '
                                f'host_env=... (hostenv.DeepSeaTreasureHostVecEnv, --host-env dst) or device_env=True '
                                f'(--device-env)')
@@ -159,6 +185,15 @@ class TaskBatch:
             if self.max_steps <= 0 or not self.bound > 0 or self.R < 1:
                 raise PGMError(f'{env_name}: max_steps={self.max_steps}, bound={self.bound} and R={self.R} must be '
                                f'positive')
+        if self.plugin is not None:
+            if self.plugin.dims() != (self.O, self.A, self.K) or self.plugin.DISCRETE != self.discrete:
+                raise PGMError(f'env_plugin has (obs, act, obj) dims {self.plugin.dims()}, discrete = '
+                               f'{self.plugin.DISCRETE}; {env_name} is registered with {(self.O, self.A, self.K)}, '
+                               f'discrete = {self.discrete}')
+            from . import envplug
+            self.R = int(envplug.DEFAULT_RESETS if R is None else R)
+            if self.R < 1:
+                raise PGMError(f'{env_name}: R={self.R} reset-table entries per env must be at least 1')
         self.act_width = 1 if self.discrete else self.A
         self.layout = ParamLayout(self.O, self.A, self.K, self.H, layernorm=self.layernorm, discrete=self.discrete)
         L, O, A, K, N, T = self.layout.total, self.O, self.A, self.K, self.N, self.T
@@ -196,6 +231,16 @@ class TaskBatch:
             self._dummy_train = torch.tensor(envspec.dummy_reset_table(seed, N, self.R), dtype=F64, device=self.dev)
             self._dummy_eval = torch.tensor(envspec.dummy_reset_table(seed, eval_num, self.R), dtype=F64,
                                             device=self.dev)
+        if self.plugin is not None:  # the plug-in's state words, resets since env_reset(), the reset uniforms
+            pl = self.plugin
+            z('plug_sd', N, pl.SD, dt=F64)
+            z('plug_si', N, pl.SI, dt=I32)
+            z('episode', N, dt=I32)
+            self._plug_train_np = envspec.plugin_reset_table(seed, N, self.R, pl.RW)
+            self._plug_train = torch.tensor(self._plug_train_np, dtype=F64, device=self.dev)
+            self._plug_eval = torch.tensor(envspec.plugin_reset_table(seed, eval_num, self.R, pl.RW), dtype=F64,
+                                           device=self.dev)
+            self._plug_obs0 = torch.zeros(Pc, N, O, dtype=F64, device=self.dev)
         # rollout storage (storage.py:12-30)
         z('obs', T + 1, N, O)
         z('actions', T, N, self.act_width)
@@ -493,6 +538,19 @@ class TaskBatch:
                                        C.byref(self.c_rb), -1, _ptr(self._dst_obs0), None, None, None, None,
                                        _stream()), 'pgm_env_ingest')
             return self.obs[:, 0]
+        if self.plugin is not None:  # env n of every task at entry (n, 0) of its row: the header's reset on the host
+            P, N, pl = self.P, self.N, self.plugin
+            row = np.broadcast_to(np.arange(N, dtype=np.int32), (P, N)).reshape(-1)
+            sd, si, obs = pl.reset(row, np.zeros(P * N, dtype=np.int32), self._plug_train_np)
+            self.plug_sd.copy_(torch.from_numpy(sd.reshape(P, N, pl.SD)))
+            self.plug_si.copy_(torch.from_numpy(si.reshape(P, N, pl.SI)))
+            self._plug_obs0[:P].copy_(torch.from_numpy(obs.reshape(P, N, self.O)))
+            self.elapsed.zero_()
+            self.episode.zero_()
+            check(lib().pgm_env_ingest_any(C.byref(self.dims), C.byref(self.c_state), C.byref(self.c_norm),
+                                           C.byref(self.c_rb), -1, _ptr(self._plug_obs0), None, None, None, None,
+                                           _stream()), 'pgm_env_ingest_any')
+            return self.obs[:, 0]
         if self.dummy_env:  # env n of every task at entry (n, 0) of the reset table, at rest; VecNormalize.reset
             self.s.zero_()
             self.s[:, :, :2] = self._dummy_train[:, 0]
@@ -511,6 +569,9 @@ class TaskBatch:
         return out
 
     def env_step(self, action):
+        if self.plugin is not None:
+            raise PGMError('env_step: an env plug-in is stepped inside pgm_envplug_rollout / pgm_envplug_eval; there '
+                           'is no single-step kernel (EnvPlugin.transition evaluates the header on the host)')
         if self.any_dims:
             raise PGMError('env_step: this batch runs on the runtime-dim kernels, which are host-stepped only: the '
                            'environments are stepped inside rollout(), there is no device env to step')
@@ -561,6 +622,14 @@ class TaskBatch:
             if noise is not self.noise:
                 self.noise.copy_(noise.to(dtype=F32))
             nz = self.noise
+        if self.plugin is not None:  # noise: normals [T][N][A] / uniforms [T][N]; None: the counter stream of `seed`
+            pl = self.plugin
+            pl.check(pl.h.pgm_envplug_rollout(C.byref(self.dims), _ptr(self.params), _ptr(self.plug_sd),
+                                              _ptr(self.plug_si), _ptr(self.episode), _ptr(self._plug_train), self.R,
+                                              self.N, C.byref(self.c_state), C.byref(self.c_norm), C.byref(self.c_rb),
+                                              _ptr(nz), C.c_uint64(seed), int(carry), _stream()),
+                     'pgm_envplug_rollout')
+            return
         if self.device_env:  # noise: uniforms [T][N]; None: the kernel draws pgm_uniform_noise's stream of `seed`
             check(lib().pgm_rollout_dst(C.byref(self.dims), _ptr(self.params), C.byref(self.c_dst),
                                         C.byref(self.c_state), C.byref(self.c_norm), C.byref(self.c_rb), _ptr(nz),
@@ -660,6 +729,12 @@ class TaskBatch:
         out = self.objs if out is None else out
         if self.host_env is not None:
             return self._host_evaluate(mean, var, out)
+        if self.plugin is not None:
+            pl = self.plugin
+            pl.check(pl.h.pgm_envplug_eval(C.byref(self.dims), _ptr(self.params), _ptr(self._plug_eval), self.R,
+                                           self.eval_num, _ptr(mean), _ptr(var), self.eval_num, int(self.use_ob_rms),
+                                           int(self.raw), self.gamma, _ptr(out), _stream()), 'pgm_envplug_eval')
+            return out
         if self.device_env:
             check(lib().pgm_eval_dst(C.byref(self.dims), _ptr(self.params), C.byref(self.c_dst), _ptr(mean), _ptr(var),
                                      self.eval_num, int(self.use_ob_rms), int(self.raw), self.gamma, _ptr(out),
@@ -707,7 +782,7 @@ class TaskBatch:
             overlap_eval = False
         # perf mode: the counter stream of iteration j, drawn by one wide kernel up front (the fused Deep Sea Treasure
         # and MO-Dummy rollouts draw the same stream inside the kernel: noise stays None)
-        if noise is None and not self.device_env and not self.dummy_env:
+        if noise is None and not self.device_env and not self.dummy_env and self.plugin is None:
             self._draw_noise(j)
             noise = self.noise
         perm_ready = None

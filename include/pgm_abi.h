@@ -313,6 +313,29 @@ int pgm_eval(const pgm_dims* d, const float* params, const pgm_env_spec* spec, c
              const double* ob_var, const double* s0_eval, int32_t eval_num, int32_t use_ob_rms, int32_t raw,
              double gamma, double* objs_out, const pgm_launch_opts* opts, pgm_stream_t stream);
 
+/* ---- Several runs in one population (discovered by the presence of the symbol pgm_rollout_runs; no feature bit, no
+ * version change).  The tasks of several runs of a sweep (one seed each, a2c_ppo_acktr/envs.py make_env(seed + rank)
+ * per env process; the launchers scripts/<env>.py start --num-seeds of them per selection method) share one device
+ * population.  Action noise, minibatch permutations and the learning-rate schedule depend on the iteration only
+ * (morl/mopg.py:96), so the one thing a run owns on the device is its reset state.  run_of_task is a DEVICE int32 [P];
+ * st->s0 is read as [num_runs][N][O] and s0_eval as [num_runs][eval_num][O]; task p uses block run_of_task[p] at its
+ * initial reset, at every auto-reset and at every evaluation start.  Nothing else differs from pgm_env_reset /
+ * pgm_rollout / pgm_eval: the arithmetic, the thread roles, the stored fields, the counter streams keyed by `seed`, the
+ * kernel families and pgm_launch_opts; with num_runs = 1 and all-zero ids the outputs are theirs bit for bit.
+ * Validation: every check of the entry point each extends, in its order and with its strings; then a NULL run_of_task
+ * or num_runs < 1 is PGM_E_INVALID_ARG naming the _runs entry point.  The ids are device memory and are not read on
+ * the host: the caller guarantees 0 <= run_of_task[p] < num_runs. */
+int pgm_env_reset_runs(const pgm_dims* d, const pgm_env_spec* spec, const pgm_env_state* st, const pgm_norm_state* ns,
+                       const int32_t* run_of_task, int32_t num_runs, float* obs_out, pgm_stream_t stream);
+int pgm_rollout_runs(const pgm_dims* d, const float* params, const pgm_env_spec* spec, const pgm_env_state* st,
+                     const pgm_norm_state* ns, const pgm_rollout_buf* rb, const float* noise, uint64_t seed,
+                     int32_t carry, const int32_t* run_of_task, int32_t num_runs, const pgm_launch_opts* opts,
+                     pgm_stream_t stream);
+int pgm_eval_runs(const pgm_dims* d, const float* params, const pgm_env_spec* spec, const double* ob_mean,
+                  const double* ob_var, const double* s0_eval, int32_t eval_num, int32_t use_ob_rms, int32_t raw,
+                  double gamma, double* objs_out, const int32_t* run_of_task, int32_t num_runs,
+                  const pgm_launch_opts* opts, pgm_stream_t stream);
+
 /* ---- Host-stepped environments (from minor 1).  The environments run on the host; policy, VecNormalize
  * statistics, rollout storage and the PPO update stay on the device.  One rollout step t is
  *     pgm_rollout_act(t) -> copy action_out to the host -> envs.step(actions) -> copy the transition to the device

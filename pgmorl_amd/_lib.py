@@ -161,7 +161,16 @@ _SIGS = {
     'pgm_ppo_update_any': (C.c_int, [C.POINTER(Dims), I32, C.POINTER(PPOHParams), P_, P_, P_, P_, P_, P_,
                                      C.POINTER(RolloutBuf), P_, P_, P_]),
     'pgm_ppo_update_any_workspace_bytes': (C.c_size_t, [C.POINTER(Dims)]),
+    # several runs of a sweep in one population (no feature bit: discovered by the symbol pgm_rollout_runs);
+    # run_of_task (device int32 [P]) and num_runs sit before obs_out / opts
+    'pgm_env_reset_runs': (C.c_int, [C.POINTER(Dims), C.POINTER(EnvSpec), C.POINTER(EnvState), C.POINTER(NormState),
+                                     P_, I32, P_, P_]),
+    'pgm_rollout_runs': (C.c_int, [C.POINTER(Dims), P_, C.POINTER(EnvSpec), C.POINTER(EnvState), C.POINTER(NormState),
+                                   C.POINTER(RolloutBuf), P_, C.c_uint64, I32, P_, I32, C.POINTER(LaunchOpts), P_]),
+    'pgm_eval_runs': (C.c_int, [C.POINTER(Dims), P_, C.POINTER(EnvSpec), P_, P_, P_, I32, I32, I32, F64, P_, P_, I32,
+                                C.POINTER(LaunchOpts), P_]),
 }
+RUNS_SYMBOLS = ('pgm_env_reset_runs', 'pgm_rollout_runs', 'pgm_eval_runs')
 # the symbols a library of the same ABI version and minor may lack: discovered through pgm_abi_features
 FEATURE_CATEGORICAL = 1
 FEATURE_DST_DEVICE = 2
@@ -196,8 +205,8 @@ def _load(path):
             raise PGMError(f'{path} not built; run `python -m pgmorl_amd.build` (hipcc, gfx950)')
         h = C.CDLL(path)
         for name, (res, args) in _SIGS.items():
-            if name in _FEATURE_SYMBOLS and not hasattr(h, name):
-                continue  # an older library of this ABI: features() reports what is missing
+            if (name in _FEATURE_SYMBOLS or name in RUNS_SYMBOLS) and not hasattr(h, name):
+                continue  # an older library of this ABI: features() / has_runs() report what is missing
             f = getattr(h, name)
             f.restype, f.argtypes = res, args
         if h.pgm_abi_version() != PGM_ABI_VERSION:
@@ -268,6 +277,18 @@ def require_dummy_device():
 def require_any_dims():
     if not features() & FEATURE_ANY_DIMS:
         raise PGMError('this libpgm.so has no runtime-dim entry points (pgm_abi_feature_mask() & 8 is clear); '
+                       'rebuild it with `python -m pgmorl_amd.build`')
+
+
+def has_runs():
+    """True if the library has the *_runs entry points (several runs in one population): the presence of the symbol
+    pgm_rollout_runs, as include/pgm_abi.h documents (there is no feature bit)."""
+    return hasattr(lib(), 'pgm_rollout_runs')
+
+
+def require_runs():
+    if not has_runs():
+        raise PGMError('this libpgm.so has no pgm_rollout_runs (the per-run reset tables of a batched sweep); '
                        'rebuild it with `python -m pgmorl_amd.build`')
 
 

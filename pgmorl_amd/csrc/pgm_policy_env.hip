@@ -66,12 +66,21 @@ struct EnvArgs {
     int reset;
 };
 
-template <int O, int A, int K>
-__global__ __launch_bounds__(RT) void env_kernel(EnvArgs a) {
+struct EnvRunsArgs : EnvArgs {
+    const int32_t* run_of_task;  // [P], device (pgm_env_reset_runs)
+};
+template <bool RUNS>
+using EnvArgsT = std::conditional_t<RUNS, EnvRunsArgs, EnvArgs>;
+
+// RUNS (here and in the two kernels below): the reset table is stacked per run, and the task's block is selected once,
+// before Spec / load_spec take the pointer (pgm_rollout.hpp)
+template <int O, int A, int K, bool RUNS>
+__global__ __launch_bounds__(RT) void env_kernel(EnvArgsT<RUNS> a) {
     extern __shared__ __attribute__((aligned(16))) char smem_raw[];
     auto& S = *reinterpret_cast<StepSmem<O, A, K>*>(smem_raw);
     auto& E = S.env;
     const int p = blockIdx.x, t = threadIdx.x, N = a.N;
+    if constexpr (RUNS) a.st.s0 += (size_t)a.run_of_task[p] * N * O;
     const NormCfg nc = norm_cfg(a.ns);
     const Spec<O, A, K> sp{E, a.spec, a.st.s0};
     load_spec(E, a.spec, a.st.s0, N);
@@ -103,13 +112,14 @@ __global__ __launch_bounds__(RT) void env_kernel(EnvArgs a) {
 }
 
 // fused rollout, block form (Gaussian head on the device envs).  L is the towers' layout (a.L for the plain ones).
-template <class Tw, int O, int A, int K>
-__global__ __launch_bounds__(RT) void rollout_kernel(RolloutArgs a, typename Tw::Lay L) {
+template <class Tw, int O, int A, int K, bool RUNS>
+__global__ __launch_bounds__(RT) void rollout_kernel(RolloutArgsT<RUNS> a, typename Tw::Lay L) {
     extern __shared__ __attribute__((aligned(16))) char smem_raw[];
     auto& S = *reinterpret_cast<StepSmem<O, A, K>*>(smem_raw);
     auto& P = S.pol;
     auto& E = S.env;
     const int p = blockIdx.x, t = threadIdx.x, N = a.N, T = a.T;
+    if constexpr (RUNS) a.st.s0 += (size_t)a.run_of_task[p] * N * O;
     const NormCfg nc = norm_cfg(a.ns);
     const Spec<O, A, K> sp{E, a.spec, a.st.s0};
     const float* prm = a.params + (size_t)p * L.total;
@@ -175,13 +185,14 @@ __global__ __launch_bounds__(RT) void rollout_kernel(RolloutArgs a, typename Tw:
 }
 
 // deterministic evaluation, block form (mopg.py:25-46)
-template <class Tw, int O, int A, int K>
-__global__ __launch_bounds__(RT) void eval_kernel(EvalArgs a, typename Tw::Lay L) {
+template <class Tw, int O, int A, int K, bool RUNS>
+__global__ __launch_bounds__(RT) void eval_kernel(EvalArgsT<RUNS> a, typename Tw::Lay L) {
     extern __shared__ __attribute__((aligned(16))) char smem_raw[];
     auto& S = *reinterpret_cast<StepSmem<O, A, K>*>(smem_raw);
     auto& P = S.pol;
     auto& E = S.env;
     const int p = blockIdx.x, t = threadIdx.x;
+    if constexpr (RUNS) a.s0_eval += (size_t)a.run_of_task[p] * a.eval_num * O;
     const float* prm = a.params + (size_t)p * L.total;
     typename Tw::template Reg<O, A, K> R;
     load_policy<Tw, true>(P, R, prm, L);
@@ -268,22 +279,48 @@ static int env_common(const pgm_dims* d, const pgm_env_spec* spec, const pgm_env
     return PGM_OK;
 }
 
-static int launch_env(const pgm_dims* d, const EnvArgs& a, pgm_stream_t stream, const char* what) {
+static int launch_env(const pgm_dims* d, const EnvArgs& a, pgm_stream_t stream, const char* what,
+                      const int32_t* runs = nullptr) {
     return dispatch_dims(d->O, d->A, d->K, what, [&](auto o, auto aa, auto k) {
         constexpr int O = decltype(o)::value, A = decltype(aa)::value, K = decltype(k)::value;
-        return launch_smem(env_kernel<O, A, K>, d->P, sizeof(StepSmem<O, A, K>), (hipStream_t)stream, what, a);
+        if (runs)
+            return launch_smem(env_kernel<O, A, K, true>, d->P, sizeof(StepSmem<O, A, K>), (hipStream_t)stream, what,
+                               EnvRunsArgs{a, runs});
+        return launch_smem(env_kernel<O, A, K, false>, d->P, sizeof(StepSmem<O, A, K>), (hipStream_t)stream, what, a);
     });
 }
 
-int pgm_env_reset(const pgm_dims* d, const pgm_env_spec* spec, const pgm_env_state* st,
-                  const pgm_norm_state* ns, float* obs_out, pgm_stream_t stream) {
+// the *_runs entry points' own check, after every check of the entry point they extend
+static int check_runs(const int32_t* run_of_task, int32_t num_runs, const char* what) {
+    if (!run_of_task || num_runs < 1) {
+        set_error("%s: run_of_task is NULL or num_runs < 1", what);
+        return PGM_E_INVALID_ARG;
+    }
+    return PGM_OK;
+}
+
+// pgm_env_reset and pgm_env_reset_runs (runs: the second one's run_of_task / num_runs, checked last)
+static int env_reset_impl(const pgm_dims* d, const pgm_env_spec* spec, const pgm_env_state* st, const pgm_norm_state* ns,
+                          float* obs_out, pgm_stream_t stream, const int32_t* const* runs, int32_t num_runs) {
     if (int rc = env_common(d, spec, st, ns, "pgm_env_reset")) return rc;
     if (!obs_out) {
         set_error("pgm_env_reset: null obs_out");
         return PGM_E_INVALID_ARG;
     }
+    if (runs)
+        if (int rc = check_runs(*runs, num_runs, "pgm_env_reset_runs")) return rc;
     return launch_env(d, EnvArgs{d->P, d->N, *spec, *st, *ns, nullptr, obs_out, nullptr, nullptr, nullptr, 1}, stream,
-                      "pgm_env_reset");
+                      runs ? "pgm_env_reset_runs" : "pgm_env_reset", runs ? *runs : nullptr);
+}
+
+int pgm_env_reset(const pgm_dims* d, const pgm_env_spec* spec, const pgm_env_state* st,
+                  const pgm_norm_state* ns, float* obs_out, pgm_stream_t stream) {
+    return env_reset_impl(d, spec, st, ns, obs_out, stream, nullptr, 0);
+}
+
+int pgm_env_reset_runs(const pgm_dims* d, const pgm_env_spec* spec, const pgm_env_state* st, const pgm_norm_state* ns,
+                       const int32_t* run_of_task, int32_t num_runs, float* obs_out, pgm_stream_t stream) {
+    return env_reset_impl(d, spec, st, ns, obs_out, stream, &run_of_task, num_runs);
 }
 
 int pgm_env_step(const pgm_dims* d, const pgm_env_spec* spec, const pgm_env_state* st,
@@ -298,9 +335,10 @@ int pgm_env_step(const pgm_dims* d, const pgm_env_spec* spec, const pgm_env_stat
                       stream, "pgm_env_step");
 }
 
-int pgm_rollout(const pgm_dims* d, const float* params, const pgm_env_spec* spec, const pgm_env_state* st,
-                const pgm_norm_state* ns, const pgm_rollout_buf* rb, const float* noise, uint64_t seed,
-                int32_t carry, const pgm_launch_opts* opts, pgm_stream_t stream) {
+static int rollout_impl(const pgm_dims* d, const float* params, const pgm_env_spec* spec, const pgm_env_state* st,
+                        const pgm_norm_state* ns, const pgm_rollout_buf* rb, const float* noise, uint64_t seed,
+                        int32_t carry, const pgm_launch_opts* opts, pgm_stream_t stream, const int32_t* const* runs_arg,
+                        int32_t num_runs) {
     if (int rc = env_common(d, spec, st, ns, "pgm_rollout")) return rc;
     if (int rc = check_ln(d, "pgm_rollout")) return rc;
     pgm_launch_opts o;
@@ -314,23 +352,45 @@ int pgm_rollout(const pgm_dims* d, const float* params, const pgm_env_spec* spec
         set_error("pgm_rollout: T must be positive");
         return PGM_E_SHAPE;
     }
+    const int32_t* runs = nullptr;
+    if (runs_arg) {
+        if (int rc = check_runs(*runs_arg, num_runs, "pgm_rollout_runs")) return rc;
+        runs = *runs_arg;
+    }
     RolloutArgs a{d->P, d->N, d->T, make_layout(d->O, d->A, d->K, d->H), params, *spec, *st, *ns, *rb,
                   noise, seed, carry};
     // LayerNorm towers: one kernel family, opts ignored; plain: the block kernel on request (A/B, tests) or last
     if (!d->LN && o.rollout_kernel != 1) {
-        if (rollout_lanes_supported(d)) return launch_rollout_lanes(d, a, (hipStream_t)stream);
-        if (rollout_wide_supported(d)) return launch_rollout_wide(d, a, (hipStream_t)stream);
+        if (rollout_lanes_supported(d)) return launch_rollout_lanes(d, a, (hipStream_t)stream, runs);
+        if (rollout_wide_supported(d)) return launch_rollout_wide(d, a, (hipStream_t)stream, runs);
     }
     return dispatch_towers(d, "pgm_rollout", [&](auto tw, const auto& L, auto o, auto aa, auto k) {
         constexpr int O = decltype(o)::value, A = decltype(aa)::value, K = decltype(k)::value;
-        return launch_smem(rollout_kernel<decltype(tw), O, A, K>, d->P, sizeof(StepSmem<O, A, K>), (hipStream_t)stream,
-                           "pgm_rollout", a, L);
+        if (runs)
+            return launch_smem(rollout_kernel<decltype(tw), O, A, K, true>, d->P, sizeof(StepSmem<O, A, K>),
+                               (hipStream_t)stream, "pgm_rollout_runs", RolloutRunsArgs{a, runs}, L);
+        return launch_smem(rollout_kernel<decltype(tw), O, A, K, false>, d->P, sizeof(StepSmem<O, A, K>),
+                           (hipStream_t)stream, "pgm_rollout", a, L);
     });
 }
 
-int pgm_eval(const pgm_dims* d, const float* params, const pgm_env_spec* spec, const double* ob_mean,
-             const double* ob_var, const double* s0_eval, int32_t eval_num, int32_t use_ob_rms, int32_t raw,
-             double gamma, double* objs_out, const pgm_launch_opts* opts, pgm_stream_t stream) {
+int pgm_rollout(const pgm_dims* d, const float* params, const pgm_env_spec* spec, const pgm_env_state* st,
+                const pgm_norm_state* ns, const pgm_rollout_buf* rb, const float* noise, uint64_t seed,
+                int32_t carry, const pgm_launch_opts* opts, pgm_stream_t stream) {
+    return rollout_impl(d, params, spec, st, ns, rb, noise, seed, carry, opts, stream, nullptr, 0);
+}
+
+int pgm_rollout_runs(const pgm_dims* d, const float* params, const pgm_env_spec* spec, const pgm_env_state* st,
+                     const pgm_norm_state* ns, const pgm_rollout_buf* rb, const float* noise, uint64_t seed,
+                     int32_t carry, const int32_t* run_of_task, int32_t num_runs, const pgm_launch_opts* opts,
+                     pgm_stream_t stream) {
+    return rollout_impl(d, params, spec, st, ns, rb, noise, seed, carry, opts, stream, &run_of_task, num_runs);
+}
+
+static int eval_impl(const pgm_dims* d, const float* params, const pgm_env_spec* spec, const double* ob_mean,
+                     const double* ob_var, const double* s0_eval, int32_t eval_num, int32_t use_ob_rms, int32_t raw,
+                     double gamma, double* objs_out, const pgm_launch_opts* opts, pgm_stream_t stream,
+                     const int32_t* const* runs_arg, int32_t num_runs) {
     if (int rc = check_dims(d, "pgm_eval")) return rc;
     if (int rc = check_ln(d, "pgm_eval")) return rc;
     pgm_launch_opts o;
@@ -339,17 +399,40 @@ int pgm_eval(const pgm_dims* d, const float* params, const pgm_env_spec* spec, c
         set_error("pgm_eval: bad arguments");
         return PGM_E_INVALID_ARG;
     }
+    const int32_t* runs = nullptr;
+    if (runs_arg) {
+        if (int rc = check_runs(*runs_arg, num_runs, "pgm_eval_runs")) return rc;
+        runs = *runs_arg;
+    }
     EvalArgs a{d->P, make_layout(d->O, d->A, d->K, d->H), params, *spec, ob_mean, ob_var, s0_eval,
                eval_num, use_ob_rms, raw, gamma, objs_out};
     // LayerNorm towers: one kernel family, opts ignored; plain: the block kernel on request (A/B, tests) or last
     if (!d->LN && o.eval_kernel != 1) {
-        if (eval_waves_supported(d, eval_num)) return launch_eval_waves(d, a, (hipStream_t)stream);
-        if (eval_wide_supported(d, eval_num)) return launch_eval_wide(d, a, (hipStream_t)stream);
+        if (eval_waves_supported(d, eval_num)) return launch_eval_waves(d, a, (hipStream_t)stream, runs);
+        if (eval_wide_supported(d, eval_num)) return launch_eval_wide(d, a, (hipStream_t)stream, runs);
     }
     return dispatch_towers(d, "pgm_eval", [&](auto tw, const auto& L, auto o, auto aa, auto k) {
         constexpr int O = decltype(o)::value, A = decltype(aa)::value, K = decltype(k)::value;
-        return launch_smem(eval_kernel<decltype(tw), O, A, K>, d->P, sizeof(StepSmem<O, A, K>), (hipStream_t)stream,
-                           "pgm_eval", a, L);
+        if (runs)
+            return launch_smem(eval_kernel<decltype(tw), O, A, K, true>, d->P, sizeof(StepSmem<O, A, K>),
+                               (hipStream_t)stream, "pgm_eval_runs", EvalRunsArgs{a, runs}, L);
+        return launch_smem(eval_kernel<decltype(tw), O, A, K, false>, d->P, sizeof(StepSmem<O, A, K>),
+                           (hipStream_t)stream, "pgm_eval", a, L);
     });
+}
+
+int pgm_eval(const pgm_dims* d, const float* params, const pgm_env_spec* spec, const double* ob_mean,
+             const double* ob_var, const double* s0_eval, int32_t eval_num, int32_t use_ob_rms, int32_t raw,
+             double gamma, double* objs_out, const pgm_launch_opts* opts, pgm_stream_t stream) {
+    return eval_impl(d, params, spec, ob_mean, ob_var, s0_eval, eval_num, use_ob_rms, raw, gamma, objs_out, opts, stream,
+                     nullptr, 0);
+}
+
+int pgm_eval_runs(const pgm_dims* d, const float* params, const pgm_env_spec* spec, const double* ob_mean,
+                  const double* ob_var, const double* s0_eval, int32_t eval_num, int32_t use_ob_rms, int32_t raw,
+                  double gamma, double* objs_out, const int32_t* run_of_task, int32_t num_runs,
+                  const pgm_launch_opts* opts, pgm_stream_t stream) {
+    return eval_impl(d, params, spec, ob_mean, ob_var, s0_eval, eval_num, use_ob_rms, raw, gamma, objs_out, opts, stream,
+                     &run_of_task, num_runs);
 }
 }  // extern "C"

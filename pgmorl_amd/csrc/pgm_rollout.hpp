@@ -2,6 +2,8 @@
 // launchers of the lane-parallel kernels (pgm_rollout_lanes.hip) used by the entry points in
 // pgm_policy_env.hip.
 #pragma once
+#include <type_traits>
+
 #include "pgm_common.hpp"
 
 namespace pgm {
@@ -208,19 +210,35 @@ struct EvalArgs {
     double* objs;
 };
 
+// The *_runs entry points (several runs of a sweep in one population): task p resets from block run_of_task[p] of the
+// stacked reset tables, st.s0 [num_runs][N][O] / s0_eval [num_runs][eval_num][O].  A kernel instantiated with RUNS moves
+// its table pointer to the task's block once, before anything reads it; the RUNS = false instantiation is the kernel as
+// it was (the argument block included).
+struct RolloutRunsArgs : RolloutArgs {
+    const int32_t* run_of_task;  // [P], device
+};
+struct EvalRunsArgs : EvalArgs {
+    const int32_t* run_of_task;  // [P], device
+};
+template <bool RUNS>
+using RolloutArgsT = std::conditional_t<RUNS, RolloutRunsArgs, RolloutArgs>;
+template <bool RUNS>
+using EvalArgsT = std::conditional_t<RUNS, EvalRunsArgs, EvalArgs>;
+
 // Lane-parallel kernels (pgm_rollout_lanes.hip).  Each returns PGM_E_UNSUPPORTED without launching when
 // the dims are outside its envelope (the caller then uses the block-per-task kernel).
-int launch_rollout_lanes(const pgm_dims* d, const RolloutArgs& a, hipStream_t stream);
-int launch_eval_waves(const pgm_dims* d, const EvalArgs& a, hipStream_t stream);
+// (runs != nullptr: the RUNS instantiation with that run_of_task)
+int launch_rollout_lanes(const pgm_dims* d, const RolloutArgs& a, hipStream_t stream, const int32_t* runs = nullptr);
+int launch_eval_waves(const pgm_dims* d, const EvalArgs& a, hipStream_t stream, const int32_t* runs = nullptr);
 bool rollout_lanes_supported(const pgm_dims* d);
 bool eval_waves_supported(const pgm_dims* d, int eval_num);
 // critic values of every stored observation (value_kernel, after an actor-only rollout)
 int launch_critic_values(const pgm_dims* d, const RolloutArgs& a, hipStream_t stream);
 // wide-observation rollout (pgm_rollout_wide.hip): 48 < obs_dim <= 448, N in {1, 2, 4, 8}, N*K <= 16
 bool rollout_wide_supported(const pgm_dims* d);
-int launch_rollout_wide(const pgm_dims* d, const RolloutArgs& a, hipStream_t stream);
+int launch_rollout_wide(const pgm_dims* d, const RolloutArgs& a, hipStream_t stream, const int32_t* runs = nullptr);
 // wide-observation evaluation (pgm_rollout_wide.hip): 48 < obs_dim <= 512, eval_num <= 8, eval_num*K <= 16
 bool eval_wide_supported(const pgm_dims* d, int eval_num);
-int launch_eval_wide(const pgm_dims* d, const EvalArgs& a, hipStream_t stream);
+int launch_eval_wide(const pgm_dims* d, const EvalArgs& a, hipStream_t stream, const int32_t* runs = nullptr);
 
 }  // namespace pgm

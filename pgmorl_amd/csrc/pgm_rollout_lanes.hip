@@ -353,14 +353,15 @@ __device__ __forceinline__ double clipd_s(double x, double lo, double hi) {
 // (Measured and dropped: the two roles in two workgroups per task, the chain streaming its states, action-mean rows and
 // done flags to a scratch with sc1 stores and publishing every 16 steps -- 2.31 vs 1.91 ms per Walker P = 40 rollout:
 // every publish drains the chain's sc1 stores and each chunk's loads pay a memory round trip.)
-template <int O, int A, int K, int NN>
-__global__ __launch_bounds__(512) void rollout_lane_kernel(RolloutArgs a) {
+template <int O, int A, int K, int NN, bool RUNS>
+__global__ __launch_bounds__(512) void rollout_lane_kernel(RolloutArgsT<RUNS> a) {
     static_assert(lanes_fit<O, K>(), "lane roles need O + K + 1 <= 64");
     constexpr int NW = NN < 4 ? NN : 4;  // waves per role
     constexpr int NE = (NN + 3) / 4;     // env slots per wave
     extern __shared__ __attribute__((aligned(16))) char smem_raw[];
     auto& S = *reinterpret_cast<LaneSmem<O, A, NN>*>(smem_raw);
     const int p = (int)blockIdx.x, l = threadIdx.x & 63;
+    if constexpr (RUNS) a.st.s0 += (size_t)a.run_of_task[p] * NN * O;  // the task's run: its [N][O] reset block
     const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const bool chain = wv < NW;
     const int w = chain ? wv : wv - NW;  // env slot base of this wave
@@ -1004,12 +1005,13 @@ struct EvalSmem {
 };
 constexpr int EVAL_MAX_WAVES = 8, EVAL_MAX_EPISODES = 64;
 
-template <int O, int A, int K>
-__global__ __launch_bounds__(64 * EVAL_MAX_WAVES) void eval_wave_kernel(EvalArgs a) {
+template <int O, int A, int K, bool RUNS>
+__global__ __launch_bounds__(64 * EVAL_MAX_WAVES) void eval_wave_kernel(EvalArgsT<RUNS> a) {
     static_assert(K <= 4, "epi rows hold 4 objectives");
     extern __shared__ __attribute__((aligned(16))) char smem_raw[];
     auto& S = *reinterpret_cast<EvalSmem<O>*>(smem_raw);
     const int p = blockIdx.x, l = threadIdx.x & 63;
+    if constexpr (RUNS) a.s0_eval += (size_t)a.run_of_task[p] * a.eval_num * O;  // the task's run: its [eval_num][O] block
     const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int nw = blockDim.x >> 6;
     const float* prm = a.params + (size_t)p * a.L.total;
@@ -1079,10 +1081,10 @@ bool eval_waves_supported(const pgm_dims* d, int eval_num) {
     return lanes_dims(d->O, d->K) && d->K <= 4 && eval_num <= EVAL_MAX_EPISODES;
 }
 
-template <int O, int A, int K, int NN>
-static int launch_rollout_n(const pgm_dims* d, const RolloutArgs& a, hipStream_t s) {
+template <int O, int A, int K, int NN, bool RUNS>
+static int launch_rollout_n(const pgm_dims* d, const RolloutArgsT<RUNS>& a, hipStream_t s) {
     constexpr int NW = NN < 4 ? NN : 4;
-    if (int rc = launch_k(rollout_lane_kernel<O, A, K, NN>, dim3(d->P), dim3(2 * 64 * NW), sizeof(LaneSmem<O, A, NN>), s,
+    if (int rc = launch_k(rollout_lane_kernel<O, A, K, NN, RUNS>, dim3(d->P), dim3(2 * 64 * NW), sizeof(LaneSmem<O, A, NN>), s,
                           a, "pgm_rollout"))
         return rc;
     return launch_critic_values(d, a, s);
@@ -1105,18 +1107,23 @@ int launch_critic_values(const pgm_dims* d, const RolloutArgs& a, hipStream_t s)
     });
 }
 
-int launch_rollout_lanes(const pgm_dims* d, const RolloutArgs& a, hipStream_t stream) {
+int launch_rollout_lanes(const pgm_dims* d, const RolloutArgs& a, hipStream_t stream, const int32_t* runs) {
     return dispatch_dims(d->O, d->A, d->K, "pgm_rollout", [&](auto o, auto aa, auto k) -> int {
         constexpr int O = decltype(o)::value, A = decltype(aa)::value, K = decltype(k)::value;
         if constexpr (!lanes_fit<O, K>()) {
             set_error("pgm_rollout: obs_dim %d outside the lane kernel", O);
             return PGM_E_UNSUPPORTED;
         } else {
+            auto go = [&](auto nn) -> int {
+                constexpr int NN = decltype(nn)::value;
+                if (runs) return launch_rollout_n<O, A, K, NN, true>(d, RolloutRunsArgs{a, runs}, stream);
+                return launch_rollout_n<O, A, K, NN, false>(d, a, stream);
+            };
             switch (d->N) {
-                case 1: return launch_rollout_n<O, A, K, 1>(d, a, stream);
-                case 2: return launch_rollout_n<O, A, K, 2>(d, a, stream);
-                case 4: return launch_rollout_n<O, A, K, 4>(d, a, stream);
-                case 8: return launch_rollout_n<O, A, K, 8>(d, a, stream);
+                case 1: return go(std::integral_constant<int, 1>{});
+                case 2: return go(std::integral_constant<int, 2>{});
+                case 4: return go(std::integral_constant<int, 4>{});
+                case 8: return go(std::integral_constant<int, 8>{});
             }
             set_error("pgm_rollout: N=%d outside the lane kernel (1, 2, 4, 8)", d->N);
             return PGM_E_UNSUPPORTED;
@@ -1124,7 +1131,7 @@ int launch_rollout_lanes(const pgm_dims* d, const RolloutArgs& a, hipStream_t st
     });
 }
 
-int launch_eval_waves(const pgm_dims* d, const EvalArgs& a, hipStream_t stream) {
+int launch_eval_waves(const pgm_dims* d, const EvalArgs& a, hipStream_t stream, const int32_t* runs) {
     return dispatch_dims(d->O, d->A, d->K, "pgm_eval", [&](auto o, auto aa, auto k) -> int {
         constexpr int O = decltype(o)::value, A = decltype(aa)::value, K = decltype(k)::value;
         if constexpr (!lanes_fit<O, K>() || K > 4) {
@@ -1132,7 +1139,10 @@ int launch_eval_waves(const pgm_dims* d, const EvalArgs& a, hipStream_t stream) 
             return PGM_E_UNSUPPORTED;
         } else {
             const int nw = a.eval_num < EVAL_MAX_WAVES ? a.eval_num : EVAL_MAX_WAVES;
-            return launch_k(eval_wave_kernel<O, A, K>, dim3(d->P), dim3(64 * nw), sizeof(EvalSmem<O>), stream, a,
+            if (runs)
+                return launch_k(eval_wave_kernel<O, A, K, true>, dim3(d->P), dim3(64 * nw), sizeof(EvalSmem<O>), stream,
+                                EvalRunsArgs{a, runs}, "pgm_eval");
+            return launch_k(eval_wave_kernel<O, A, K, false>, dim3(d->P), dim3(64 * nw), sizeof(EvalSmem<O>), stream, a,
                             "pgm_eval");
         }
     });

@@ -93,8 +93,8 @@ __device__ __forceinline__ void head_sums(const float (&pr)[A], float (&mu)[A]) 
     }
 }
 
-template <int O, int A, int K, int NN>
-__global__ __launch_bounds__(WTH) void rollout_wide_kernel(RolloutArgs a) {
+template <int O, int A, int K, int NN, bool RUNS>
+__global__ __launch_bounds__(WTH) void rollout_wide_kernel(RolloutArgsT<RUNS> a) {
     static_assert(wide_fit<O, K, NN>(), "wide rollout envelope");
     static_assert(A <= 32, "action lanes");
     constexpr int KW = wkw<O>(), OR = wrow<O>();
@@ -104,6 +104,8 @@ __global__ __launch_bounds__(WTH) void rollout_wide_kernel(RolloutArgs a) {
     extern __shared__ __attribute__((aligned(16))) char smem_raw[];
     auto& S = *reinterpret_cast<WideSmem<O, A, K, NN>*>(smem_raw);
     const int p = blockIdx.x, t = threadIdx.x, l = t & 63;
+    // the task's run: its [N][O] reset block (the half-block env index hb * NH + n below counts inside it)
+    if constexpr (RUNS) a.st.s0 += (size_t)a.run_of_task[p] * NN * O;
     const int w = __builtin_amdgcn_readfirstlane(t >> 6);
     const int T = a.T;
     const NormCfg nc = norm_cfg(a.ns);
@@ -591,8 +593,8 @@ struct WideEvalSmem {
     double t2[32];
 };
 
-template <int O, int A, int K, int NE>
-__global__ __launch_bounds__(WTH) void eval_wide_kernel(EvalArgs a) {
+template <int O, int A, int K, int NE, bool RUNS>
+__global__ __launch_bounds__(WTH) void eval_wide_kernel(EvalArgsT<RUNS> a) {
     static_assert(O > 48 && O <= 2 * WTH && NE * K <= 16, "wide eval envelope");
     constexpr int KW = wkw<O>(), OR = wrow<O>();
     constexpr int FPL = (O + WTH - 1) / WTH;
@@ -601,6 +603,7 @@ __global__ __launch_bounds__(WTH) void eval_wide_kernel(EvalArgs a) {
     extern __shared__ __attribute__((aligned(16))) char smem_raw[];
     auto& S = *reinterpret_cast<WideEvalSmem<O, A, K, NE>*>(smem_raw);
     const int p = blockIdx.x, t = threadIdx.x, l = t & 63;
+    if constexpr (RUNS) a.s0_eval += (size_t)a.run_of_task[p] * a.eval_num * O;  // the task's run: [eval_num][O] rows
     const int w = __builtin_amdgcn_readfirstlane(t >> 6);
     const Layout& L = a.L;
     const float* prm = a.params + (size_t)p * L.total;
@@ -798,28 +801,34 @@ bool eval_wide_supported(const pgm_dims* d, int eval_num) {
     return d->O > 48 && d->O <= 2 * WTH && eval_num >= 1 && eval_num <= 8 && eval_num * d->K <= 16 && d->A <= 32;
 }
 
-int launch_eval_wide(const pgm_dims* d, const EvalArgs& a, hipStream_t stream) {
+int launch_eval_wide(const pgm_dims* d, const EvalArgs& a, hipStream_t stream, const int32_t* runs) {
     return dispatch_dims(d->O, d->A, d->K, "pgm_eval", [&](auto o, auto aa, auto k) -> int {
         constexpr int O = decltype(o)::value, A = decltype(aa)::value, K = decltype(k)::value;
         if constexpr (O <= 48 || O > 2 * WTH || A > 32) {
             set_error("pgm_eval: obs_dim %d outside the wide eval kernel", O);
             return PGM_E_UNSUPPORTED;
         } else {
-            auto go = [&](auto kern, size_t smem) -> int {
+            auto launch = [&](auto kern, size_t smem, const auto& args) -> int {
                 if (smem > 160 * 1024) {
                     set_error("pgm_eval: LDS image %zu bytes exceeds 160 KiB", smem);
                     return PGM_E_UNSUPPORTED;
                 }
                 hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
                 if (e != hipSuccess) return hip_fail(e, "pgm_eval");
-                hipLaunchKernelGGL(kern, dim3(d->P), dim3(WTH), smem, stream, a);
+                hipLaunchKernelGGL(kern, dim3(d->P), dim3(WTH), smem, stream, args);
                 return launch_status("pgm_eval");
             };
+            auto go = [&](auto ne) -> int {
+                constexpr int NE = decltype(ne)::value;
+                constexpr size_t smem = sizeof(WideEvalSmem<O, A, K, NE>);
+                if (runs) return launch(eval_wide_kernel<O, A, K, NE, true>, smem, EvalRunsArgs{a, runs});
+                return launch(eval_wide_kernel<O, A, K, NE, false>, smem, a);
+            };
             const int en = a.eval_num;
-            if (en <= 1) return go(eval_wide_kernel<O, A, K, 1>, sizeof(WideEvalSmem<O, A, K, 1>));
-            if (en <= 2) return go(eval_wide_kernel<O, A, K, 2>, sizeof(WideEvalSmem<O, A, K, 2>));
-            if (en <= 4) return go(eval_wide_kernel<O, A, K, 4>, sizeof(WideEvalSmem<O, A, K, 4>));
-            if constexpr (8 * K <= 16) return go(eval_wide_kernel<O, A, K, 8>, sizeof(WideEvalSmem<O, A, K, 8>));
+            if (en <= 1) return go(std::integral_constant<int, 1>{});
+            if (en <= 2) return go(std::integral_constant<int, 2>{});
+            if (en <= 4) return go(std::integral_constant<int, 4>{});
+            if constexpr (8 * K <= 16) return go(std::integral_constant<int, 8>{});
             set_error("pgm_eval: eval_num %d outside the wide eval kernel", en);
             return PGM_E_UNSUPPORTED;
         }
@@ -831,9 +840,9 @@ bool rollout_wide_supported(const pgm_dims* d) {
            d->N * d->K <= 16 && (d->K & (d->K - 1)) == 0;
 }
 
-template <int O, int A, int K, int NN>
-static int launch_wide_n(const pgm_dims* d, const RolloutArgs& a, hipStream_t s) {
-    auto kern = rollout_wide_kernel<O, A, K, NN>;
+template <int O, int A, int K, int NN, bool RUNS>
+static int launch_wide_r(const pgm_dims* d, const RolloutArgsT<RUNS>& a, hipStream_t s) {
+    auto kern = rollout_wide_kernel<O, A, K, NN, RUNS>;
     const size_t smem = sizeof(WideSmem<O, A, K, NN>);
     if (smem > 160 * 1024) {
         set_error("pgm_rollout: LDS image %zu bytes exceeds 160 KiB", smem);
@@ -846,7 +855,13 @@ static int launch_wide_n(const pgm_dims* d, const RolloutArgs& a, hipStream_t s)
     return launch_critic_values(d, a, s);
 }
 
-int launch_rollout_wide(const pgm_dims* d, const RolloutArgs& a, hipStream_t stream) {
+template <int O, int A, int K, int NN>
+static int launch_wide_n(const pgm_dims* d, const RolloutArgs& a, hipStream_t s, const int32_t* runs) {
+    if (runs) return launch_wide_r<O, A, K, NN, true>(d, RolloutRunsArgs{a, runs}, s);
+    return launch_wide_r<O, A, K, NN, false>(d, a, s);
+}
+
+int launch_rollout_wide(const pgm_dims* d, const RolloutArgs& a, hipStream_t stream, const int32_t* runs) {
     return dispatch_dims(d->O, d->A, d->K, "pgm_rollout", [&](auto o, auto aa, auto k) -> int {
         constexpr int O = decltype(o)::value, A = decltype(aa)::value, K = decltype(k)::value;
         if constexpr (O <= 48 || O > 2 * WTH || (K & (K - 1)) != 0 || A > 32) {
@@ -854,11 +869,11 @@ int launch_rollout_wide(const pgm_dims* d, const RolloutArgs& a, hipStream_t str
             return PGM_E_UNSUPPORTED;
         } else {
             switch (d->N) {
-                case 1: return launch_wide_n<O, A, K, 1>(d, a, stream);
-                case 2: return launch_wide_n<O, A, K, 2>(d, a, stream);
-                case 4: return launch_wide_n<O, A, K, 4>(d, a, stream);
+                case 1: return launch_wide_n<O, A, K, 1>(d, a, stream, runs);
+                case 2: return launch_wide_n<O, A, K, 2>(d, a, stream, runs);
+                case 4: return launch_wide_n<O, A, K, 4>(d, a, stream, runs);
                 case 8:
-                    if constexpr (8 * K <= 16) return launch_wide_n<O, A, K, 8>(d, a, stream);
+                    if constexpr (8 * K <= 16) return launch_wide_n<O, A, K, 8>(d, a, stream, runs);
                     break;
             }
             set_error("pgm_rollout: N=%d outside the wide rollout kernel (1, 2, 4, 8 with N*K <= 16)", d->N);

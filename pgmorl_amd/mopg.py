@@ -48,8 +48,11 @@ def linear_lr(j, total_num_updates, lr, ratio=1.0):
 
 
 class MOPGPopulation:
-    def __init__(self, args, device='cuda', rng='device', host_env=None, device_env=None, env_plugin=None):
-        """host_env (default ``args.host_env``, the --host-env flag; None = the device envs): 'synth',
+    def __init__(self, args, device='cuda', rng='device', host_env=None, device_env=None, env_plugin=None,
+                 run_seeds=None):
+        """run_seeds: the seeds of the runs of a sweep that share this runtime's population (TaskBatch(run_seeds=...));
+        run() and evaluate_samples() then take the run index of every task.  One rank only.
+        host_env (default ``args.host_env``, the --host-env flag; None = the device envs): 'synth',
         'module:callable' or a factory (env_name, P, N, seed) -> hostenv.HostVecEnv.  The environments then run on
         the host and every TaskBatch of this runtime is built over a HostVecEnv of its own task slots (a rank holds
         host envs for its block of the population only).  device_env (default ``args.device_env``, the --device-env
@@ -80,6 +83,13 @@ class MOPGPopulation:
         self.host_env_factory = host_env
         self.device_env = bool(getattr(args, 'device_env', False) if device_env is None else device_env)
         self.moved_bytes = 0  # snapshot bytes this rank contributed to move_rows (multi-GPU)
+        # the process-global streams run() reseeds itself (host_draws: torch.manual_seed(j)); morl.run_many reads this
+        self.reseeds_global_streams = ('torch',) if rng == 'host' else ()
+        self.run_seeds = None if run_seeds is None else [int(x) for x in run_seeds]
+        if self.run_seeds is not None and world()[1] > 1:
+            from ._lib import PGMError
+            raise PGMError(f'run_seeds=... on {world()[1]} ranks: a multi-run population lives on one GPU '
+                           f'(multi-GPU sweeps are not built)')
 
     @property
     def layout(self):
@@ -114,7 +124,7 @@ class MOPGPopulation:
                                 entropy_coef=a.entropy_coef, max_grad_norm=a.max_grad_norm, device=self.device,
                                 capacity=cap, layernorm=bool(getattr(a, 'layernorm', False)), host_env=he,
                                 device_env=self.device_env,
-                                env_plugin=self.env_plugin if he is None else None)
+                                env_plugin=self.env_plugin if he is None else None, run_seeds=self.run_seeds)
         else:
             self.tb.set_active(P)
         return self.tb
@@ -211,8 +221,60 @@ class MOPGPopulation:
         if any_mismatch:
             raise RuntimeError(step_mismatch or 'Adam step counts differ from the expected ones on another rank')
 
-    def run(self, task_batch, iteration, num_updates, start_time=None, log=print):
+    @staticmethod
+    def update_fits(args, P, device='cuda'):
+        """Host-only probe: does pgm_ppo_update accept P tasks of these args' dims on this device
+        (pgm_ppo_update_variant: the launcher's own rule; the LayerNorm and wide kernels need 2P <= CUs)."""
+        import ctypes as C
+
+        from ._lib import PGM_OK, Dims, PPOHParams, launch_opts, lib
+        from .envspec import make_spec
+        sp = make_spec(args.env_name)
+        dev = torch.device(device)
+        if dev.type == 'cuda':
+            torch.cuda.set_device(dev if dev.index is not None else torch.cuda.current_device())
+        d = Dims(P, args.num_processes, args.num_steps, sp['obs_dim'], sp['act_dim'], sp['obj_num'], 64,
+                 int(bool(getattr(args, 'layernorm', False))))
+        hp = PPOHParams(clip_param=args.clip_param, value_loss_coef=args.value_loss_coef,
+                        entropy_coef=args.entropy_coef, max_grad_norm=args.max_grad_norm, adam_eps=1e-5, beta1=0.9,
+                        beta2=0.999, ppo_epoch=args.ppo_epoch, num_mini_batch=args.num_mini_batch,
+                        use_clipped_value_loss=1)
+        buf = C.create_string_buffer(128)
+        if lib().pgm_ppo_update_variant(C.byref(d), C.byref(hp), C.byref(launch_opts()), buf, 128) != PGM_OK:
+            return False
+        # pgm_ppo_update_variant names a kernel for any P; the launch itself refuses beyond the limit below
+        cus = torch.cuda.get_device_properties(dev).multi_processor_count if dev.type == 'cuda' else 0
+        return cus == 0 or P <= MOPGPopulation.update_task_limit(bool(d.LN), d.O, cus)
+
+    # The launcher's limit on P, restated (tests/test_sweep.py ties it to the text of include/pgm_abi.h and to the
+    # launchers' own refusals): the one-workgroup-per-tower updates need UPDATE_WORKGROUPS_PER_TASK * P <= CUs
+    UPDATE_WORKGROUPS_PER_TASK = 2
+    UPDATE_RESIDENT_MAX_OBS = 32  # obs_dim above it: layer 1 streamed from L2, the wide update
+
+    @staticmethod
+    def update_task_limit(layernorm, obs_dim, cus):
+        """Most tasks pgm_ppo_update accepts on a device of `cus` CUs (inf: no limit, the LDS-resident plain-tower
+        updates fall back to one workgroup per task as P grows)."""
+        if layernorm or obs_dim > MOPGPopulation.UPDATE_RESIDENT_MAX_OBS:
+            return cus // MOPGPopulation.UPDATE_WORKGROUPS_PER_TASK
+        return float('inf')
+
+    def _set_runs(self, tb, run_of_task, n):
+        """run_of_task of the n tasks just loaded (a runtime built with run_seeds; refused otherwise)."""
+        from ._lib import PGMError
+        if self.run_seeds is None:
+            if run_of_task is not None:
+                raise PGMError('run_of_task=... needs a runtime built with run_seeds=...')
+            return
+        if run_of_task is None:
+            raise PGMError(f'this runtime holds {len(self.run_seeds)} runs (run_seeds=...): run_of_task is required')
+        if len(run_of_task) != n:
+            raise PGMError(f'run_of_task has {len(run_of_task)} ids for {n} tasks')
+        tb.set_runs(run_of_task)
+
+    def run(self, task_batch, iteration, num_updates, start_time=None, log=print, run_of_task=None):
         """Every task's MOPG iterations [iteration, iteration + num_updates) -> all_offspring_batch.
+        run_of_task (with run_seeds): the run index of every task, whose reset tables it uses.
 
         Per iteration the device state of all local tasks is snapshotted by ONE copy into this generation's
         arena ([I][3][Pl][L]) and the running statistics by ONE copy of the stats64 region; the offspring
@@ -242,6 +304,7 @@ class MOPGPopulation:
             self.load_tasks(tb, [t.sample for t in task_batch[lo:hi]],
                             [t.scalarization.weights.numpy() for t in task_batch[lo:hi]])
             step0 = [t.sample.snapshot.adam_step for t in task_batch[lo:hi]]
+            self._set_runs(tb, run_of_task, Pl)
             tb.env_reset()  # envs are re-created and reset every generation (mopg.py:67-82)
             arena = torch.empty(I, 3, Pl, L, dtype=torch.float32, device=self.device)
             store = RowStore(arena, 'arena')
@@ -260,8 +323,12 @@ class MOPGPopulation:
                 if rank == 0 and a.rl_log_interval > 0 and (j + 1) % a.rl_log_interval == 0:
                     steps = (j + 1) * a.num_processes * a.num_steps
                     dt = time.time() - start_time
-                    log(f'[RL] Updates {j + 1}, num timesteps {steps}, FPS {int(steps / max(dt, 1e-9))}, '
-                        f'time {dt:.2f} seconds (x{P} tasks on {ws} device(s))')
+                    # (a sweep: one log per run, each with the line its solo run prints -- its own task count)
+                    outs = ([(log, P)] if callable(log) else
+                            [(lg, int(np.sum(np.asarray(run_of_task) == r))) for r, lg in enumerate(log)])
+                    for lg, n in outs:
+                        lg(f'[RL] Updates {j + 1}, num timesteps {steps}, FPS {int(steps / max(dt, 1e-9))}, '
+                           f'time {dt:.2f} seconds (x{n} tasks on {ws} device(s))')
             tb.wait_eval()
             if os.environ.get('PGM_DEBUG_TASKS'):
                 print(f'[debug] generation at iteration {iteration}: P={P} local={Pl} iters={I} '
@@ -326,8 +393,9 @@ class MOPGPopulation:
             o += w
         return out
 
-    def evaluate_samples(self, samples, weights_batch):
-        """Objectives of fresh samples (warm-up evaluation, morl/warm_up.py:69)."""
+    def evaluate_samples(self, samples, weights_batch, run_of_task=None):
+        """Objectives of fresh samples (warm-up evaluation, morl/warm_up.py:69); run_of_task as in run()."""
         tb = self._batch(len(samples))
         self.load_tasks(tb, samples, weights_batch)
+        self._set_runs(tb, run_of_task, len(samples))
         return tb.evaluate().cpu().numpy().copy()

@@ -31,74 +31,88 @@ def _fmt(n):
     return '{:5f}' + (n - 1) * ',{:5f}'
 
 
-def initialize_warm_up_batch(args, runtime):
-    """morl/warm_up.py:24-77: one reference-initialised policy + fresh env_params per weight, evaluated."""
-    spec = envspec.make_spec(args.env_name)
-    weights_batch = weight_grid(args.obj_num, args.delta_weight, args.min_weight, args.max_weight)
-    samples, scal = [], []
-    layout = runtime._batch(len(weights_batch)).layout
-    dev = runtime.device
-    for w in weights_batch:
-        pol = new_policy(spec['obs_dim'], spec['act_dim'], args.obj_num,
-                         layernorm=bool(getattr(args, 'layernorm', False)),
-                         discrete=bool(spec.get('discrete', False)))
-        flat = torch.from_numpy(layout.flatten(pol.state_dict())).to(dev)
-        snap = DeviceSnapshot(layout, flat, torch.zeros_like(flat), torch.zeros_like(flat), 0)
-        env_params = {'ob_rms': RunningMeanStd(shape=(spec['obs_dim'],)) if args.ob_rms else None,
-                      'ret_rms': RunningMeanStd(shape=()),
-                      'obj_rms': RunningMeanStd(shape=()) if args.obj_rms else None}
-        samples.append(Sample.from_snapshot(snap, env_params, optgraph_id=-1))
-        scal.append(WeightedSumScalarization(num_objs=args.obj_num, weights=w))
-    objs = runtime.evaluate_samples(samples, weights_batch)
-    for s, o in zip(samples, objs):
-        s.objs = o
-    return samples, scal
+class _Run:
+    """The host side of one run of the generation loop: EP, OptGraph, population, writers and timing, in pieces that
+    run() drives alone and run_many() interleaves with other runs around one shared runtime call.  The pieces are, in
+    order: __init__ (seeds the global numpy / torch streams), warm_up_samples + warm_up_done, then per generation
+    tasks -> [runtime.run] -> boundary -> [compact_snapshots] -> close_generation, and finish."""
 
+    METHODS = ('prediction-guided', 'random', 'ra', 'pfa', 'moead')
 
-def run(args, device='cuda', rng='device', log=print, runtime=None, host_env=None, device_env=None,
-        env_plugin=None):
-    """The generation loop.  ``runtime`` (default: MOPGPopulation on ``device``) is the MOPG back end: any
-    object with MOPGPopulation's run / evaluate_samples / materialize / _batch(P).layout / device.
-    ``log=None`` silences the progress lines (and skips formatting them).
-    ``host_env`` (default: ``args.host_env``, i.e. --host-env): 'synth', 'module:callable' or a factory
-    (env_name, P, N, seed) -> hostenv.HostVecEnv; the environments then run on the host (MOPGPopulation).
-    ``device_env`` (default: ``args.device_env``, i.e. --device-env): a discrete-action env runs on the device.
-    ``env_plugin`` (default: ``args.env_plugin``, i.e. --env-plugin): an envplug.EnvPlugin or the path of its header."""
-    np.random.seed(args.seed)
-    torch.manual_seed(args.seed)
-    t_start = time.perf_counter()
-    runtime = (MOPGPopulation(args, device=device, rng=rng, host_env=host_env, device_env=device_env,
-                              env_plugin=env_plugin)
-               if runtime is None else runtime)
-    template = WeightedSumScalarization(num_objs=args.obj_num, weights=np.ones(args.obj_num) / args.obj_num)
-    total_num_updates = int(args.num_env_steps) // args.num_steps // args.num_processes
-    start_time = time.time()
-    ep, opt_graph = EP(), OptGraph()
-    population = make_population(args)
-    if args.selection_method not in ('prediction-guided', 'random', 'ra', 'pfa', 'moead'):
-        raise NotImplementedError(f'selection method {args.selection_method!r}')
-    elite_batch, scalarization_batch = initialize_warm_up_batch(args, runtime)
-    for s, sc in zip(elite_batch, scalarization_batch):
-        s.optgraph_id = opt_graph.insert(deepcopy(sc.weights), deepcopy(s.objs), -1)
-    # whole-run accounting: MOPG (device iterations, incl. the end-of-generation sync and record gather)
-    # vs the generation-boundary host work (EP / population / OptGraph, selection, text dumps)
-    timing = {'init_s': time.perf_counter() - t_start, 'rl_s': 0.0, 'host_s': 0.0, 'train_env_steps': 0,
-              'generations': []}
-    rl_num_updates = args.warmup_iter
-    episode = iteration = 0
-    rank, ws = world()
-    writer = rank == 0  # every rank holds the same host state; one writes the results tree
-    gen_writer = GenerationWriter() if writer else None
-    ep_files = EPFileCache(os.path.join(args.save_dir, 'final'), gen_writer) if writer else None
-    while iteration < total_num_updates:
+    def __init__(self, args, log):
+        np.random.seed(args.seed)
+        torch.manual_seed(args.seed)
+        self.args, self.log = args, log
+        self.t_start = time.perf_counter()
+
+    def setup(self):
+        """(after the runtime exists, as run() always ordered it)"""
+        args = self.args
+        self.template = WeightedSumScalarization(num_objs=args.obj_num, weights=np.ones(args.obj_num) / args.obj_num)
+        self.total_num_updates = int(args.num_env_steps) // args.num_steps // args.num_processes
+        self.start_time = time.time()
+        self.ep, self.opt_graph = EP(), OptGraph()
+        self.population = make_population(args)
+        if args.selection_method not in self.METHODS:
+            raise NotImplementedError(f'selection method {args.selection_method!r}')
+
+    def warm_up_samples(self, runtime):
+        """morl/warm_up.py:24-68: one reference-initialised policy + fresh env_params per weight (not yet evaluated)."""
+        args = self.args
+        spec = envspec.make_spec(args.env_name)
+        weights_batch = weight_grid(args.obj_num, args.delta_weight, args.min_weight, args.max_weight)
+        samples, scal = [], []
+        layout = runtime._batch(len(weights_batch)).layout
+        dev = runtime.device
+        for w in weights_batch:
+            pol = new_policy(spec['obs_dim'], spec['act_dim'], args.obj_num,
+                             layernorm=bool(getattr(args, 'layernorm', False)),
+                             discrete=bool(spec.get('discrete', False)))
+            flat = torch.from_numpy(layout.flatten(pol.state_dict())).to(dev)
+            snap = DeviceSnapshot(layout, flat, torch.zeros_like(flat), torch.zeros_like(flat), 0)
+            env_params = {'ob_rms': RunningMeanStd(shape=(spec['obs_dim'],)) if args.ob_rms else None,
+                          'ret_rms': RunningMeanStd(shape=()),
+                          'obj_rms': RunningMeanStd(shape=()) if args.obj_rms else None}
+            samples.append(Sample.from_snapshot(snap, env_params, optgraph_id=-1))
+            scal.append(WeightedSumScalarization(num_objs=args.obj_num, weights=w))
+        self.elite_batch, self.scalarization_batch = samples, scal
+        return samples, weights_batch
+
+    def warm_up_done(self, objs):
+        args = self.args
+        for s, o in zip(self.elite_batch, objs):
+            s.objs = o
+        for s, sc in zip(self.elite_batch, self.scalarization_batch):
+            s.optgraph_id = self.opt_graph.insert(deepcopy(sc.weights), deepcopy(s.objs), -1)
+        # whole-run accounting: MOPG (device iterations, incl. the end-of-generation sync and record gather)
+        # vs the generation-boundary host work (EP / population / OptGraph, selection, text dumps)
+        self.timing = {'init_s': time.perf_counter() - self.t_start, 'rl_s': 0.0, 'host_s': 0.0, 'train_env_steps': 0,
+                       'generations': []}
+        self.rl_num_updates = args.warmup_iter
+        self.episode = self.iteration = 0
+        rank, self.ws = world()
+        self.writer = rank == 0  # every rank holds the same host state; one writes the results tree
+        self.gen_writer = GenerationWriter() if self.writer else None
+        self.ep_files = EPFileCache(os.path.join(args.save_dir, 'final'), self.gen_writer) if self.writer else None
+
+    @property
+    def done(self):
+        return self.iteration >= self.total_num_updates
+
+    def tasks(self):
+        log = self.log
         if log is not None:
-            log('\n------------------------------- Warm-up Stage -------------------------------' if episode == 0 else
-                f'\n-------------------- Evolutionary Stage: Generation {episode:3} --------------------')
-        episode += 1
-        task_batch = [Task(e, s) for e, s in zip(elite_batch, scalarization_batch)]
-        t0 = time.perf_counter()
-        all_offspring_batch = runtime.run(task_batch, iteration, rl_num_updates, start_time, log=log or (lambda *m: None))
-        t1 = time.perf_counter()
+            log('\n------------------------------- Warm-up Stage -------------------------------' if self.episode == 0
+                else f'\n-------------------- Evolutionary Stage: Generation {self.episode:3} --------------------')
+        self.episode += 1
+        self.task_batch = [Task(e, s) for e, s in zip(self.elite_batch, self.scalarization_batch)]
+        return self.task_batch
+
+    def boundary(self, all_offspring_batch):
+        """OptGraph / EP / population update, task selection, the generation's text dumps (morl/morl.py:101-221)."""
+        args, log, ep, opt_graph, population = self.args, self.log, self.ep, self.opt_graph, self.population
+        template, task_batch = self.template, self.task_batch
+        iteration, rl_num_updates, total_num_updates = self.iteration, self.rl_num_updates, self.total_num_updates
         n_its = len(all_offspring_batch[0]) if all_offspring_batch else 0
         all_sample_batch, offspring_batch = [], []
         last_offspring_batch = [None] * len(task_batch)
@@ -159,47 +173,267 @@ def run(args, device='cuda', rng='device', log=print, runtime=None, host_env=Non
             log('Selected Tasks:')
             for e, sc in zip(elite_batch, scalarization_batch):
                 log(f'objs = {e.objs}, weight = {sc.weights}')
-        iteration = min(iteration + rl_num_updates, total_num_updates)
-        rl_num_updates = args.update_iter
-        if writer:
-            gen_writer.submit(generation_record(
+        self.iteration = iteration = min(iteration + rl_num_updates, total_num_updates)
+        self.rl_num_updates = args.update_iter
+        if self.writer:
+            self.gen_writer.submit(generation_record(
                 args.save_dir, iteration, args.obj_num, ep, population, opt_graph, elite_batch, scalarization_batch,
                 all_offspring_batch, predicted_offspring_objs if args.selection_method == 'prediction-guided' else None))
-        # device memory follows the survivors (EP, population, next elites), not every offspring of the run: drop
-        # this generation's offspring lists and gather the live snapshots out of its arena
-        n_tasks = len(task_batch)
-        steps = n_tasks * n_its * args.num_steps * args.num_processes
-        del all_offspring_batch, all_sample_batch, offspring_batch, last_offspring_batch, task_batch
+        self.elite_batch, self.scalarization_batch = elite_batch, scalarization_batch
+        # device memory follows the survivors (EP, population, next elites), not every offspring of the run: the
+        # caller drops this generation's offspring lists and gathers the live snapshots out of its arena
+        self._n_tasks, self._n_its = len(task_batch), n_its
+        self.task_batch = None
+
+    def close_generation(self, rl_s, host_s):
+        """After compact_snapshots(): the EP members' final files, written ahead on the writer thread while the next
+        generation trains (its seconds are added to host_s); then the generation's timing record."""
+        t = time.perf_counter()
+        args, timing = self.args, self.timing
+        if self.writer:
+            self.ep_files.update(self.ep)
+        host_s += time.perf_counter() - t
+        timing['rl_s'] += rl_s
+        timing['host_s'] += host_s
+        timing['train_env_steps'] += self._n_tasks * self._n_its * args.num_steps * args.num_processes
+        timing['generations'].append({'iteration': self.iteration, 'tasks': self._n_tasks, 'iters': self._n_its,
+                                      'rl_s': round(rl_s, 4), 'host_s': round(host_s, 4)})
+
+    def finish(self, runtime):
+        args, ep, timing, log, ws = self.args, self.ep, self.timing, self.log, self.ws
+        t_final = time.perf_counter()
+        runtime.materialize(list(ep.sample_batch), dst=0)  # collective: EP snapshots onto the writing rank
+        if self.writer:
+            self.gen_writer.join()
+            write_final(args, ep, self.ep_files)
+            timing['final_s'] = time.perf_counter() - t_final
+            timing['wall_s'] = time.perf_counter() - self.t_start
+            timing['env_steps_per_s_whole_run'] = timing['train_env_steps'] / timing['wall_s']
+            timing['env_steps_per_s_rl_only'] = timing['train_env_steps'] / max(timing['rl_s'], 1e-9)
+            timing['host_share'] = timing['host_s'] / timing['wall_s']
+            timing['world_size'] = ws
+            with open(os.path.join(args.save_dir, 'timing.json'), 'w') as fp:
+                json.dump(timing, fp, indent=1)
+            if log is not None:
+                log(f"[timing] wall {timing['wall_s']:.2f} s: MOPG {timing['rl_s']:.2f} s, generation-boundary host "
+                    f"{timing['host_s']:.2f} s ({100 * timing['host_share']:.1f}%), {timing['train_env_steps']} train env-steps"
+                    f" -> {timing['env_steps_per_s_whole_run']:.4g} env-steps/s whole run")
+        ep.timing = timing
+        if ws > 1:
+            torch.distributed.barrier()  # the results tree is complete before any rank returns
+        return ep
+
+
+def run(args, device='cuda', rng='device', log=print, runtime=None, host_env=None, device_env=None,
+        env_plugin=None):
+    """The generation loop.  ``runtime`` (default: MOPGPopulation on ``device``) is the MOPG back end: any
+    object with MOPGPopulation's run / evaluate_samples / materialize / _batch(P).layout / device.
+    ``log=None`` silences the progress lines (and skips formatting them).
+    ``host_env`` (default: ``args.host_env``, i.e. --host-env): 'synth', 'module:callable' or a factory
+    (env_name, P, N, seed) -> hostenv.HostVecEnv; the environments then run on the host (MOPGPopulation).
+    ``device_env`` (default: ``args.device_env``, i.e. --device-env): a discrete-action env runs on the device.
+    ``env_plugin`` (default: ``args.env_plugin``, i.e. --env-plugin): an envplug.EnvPlugin or the path of its header."""
+    r = _Run(args, log)
+    runtime = (MOPGPopulation(args, device=device, rng=rng, host_env=host_env, device_env=device_env,
+                              env_plugin=env_plugin)
+               if runtime is None else runtime)
+    r.setup()
+    samples, weights_batch = r.warm_up_samples(runtime)
+    r.warm_up_done(runtime.evaluate_samples(samples, weights_batch))
+    del samples
+    while not r.done:
+        task_batch = r.tasks()
+        t0 = time.perf_counter()
+        all_offspring_batch = runtime.run(task_batch, r.iteration, r.rl_num_updates, r.start_time,
+                                          log=log or (lambda *m: None))
+        t1 = time.perf_counter()
+        r.boundary(all_offspring_batch)
+        del all_offspring_batch, task_batch
         compact_snapshots()
-        if writer:  # the EP members' final files, written ahead on the writer thread while the next generation trains
-            ep_files.update(ep)
-        t2 = time.perf_counter()
-        timing['rl_s'] += t1 - t0
-        timing['host_s'] += t2 - t1
-        timing['train_env_steps'] += steps
-        timing['generations'].append({'iteration': iteration, 'tasks': n_tasks, 'iters': n_its,
-                                      'rl_s': round(t1 - t0, 4), 'host_s': round(t2 - t1, 4)})
-    t_final = time.perf_counter()
-    runtime.materialize(list(ep.sample_batch), dst=0)  # collective: EP snapshots onto the writing rank
-    if writer:
-        gen_writer.join()
-        write_final(args, ep, ep_files)
-        timing['final_s'] = time.perf_counter() - t_final
-        timing['wall_s'] = time.perf_counter() - t_start
-        timing['env_steps_per_s_whole_run'] = timing['train_env_steps'] / timing['wall_s']
-        timing['env_steps_per_s_rl_only'] = timing['train_env_steps'] / max(timing['rl_s'], 1e-9)
-        timing['host_share'] = timing['host_s'] / timing['wall_s']
-        timing['world_size'] = ws
-        with open(os.path.join(args.save_dir, 'timing.json'), 'w') as fp:
-            json.dump(timing, fp, indent=1)
-        if log is not None:
-            log(f"[timing] wall {timing['wall_s']:.2f} s: MOPG {timing['rl_s']:.2f} s, generation-boundary host "
-                f"{timing['host_s']:.2f} s ({100 * timing['host_share']:.1f}%), {timing['train_env_steps']} train env-steps"
-                f" -> {timing['env_steps_per_s_whole_run']:.4g} env-steps/s whole run")
-    ep.timing = timing
-    if ws > 1:
-        torch.distributed.barrier()  # the results tree is complete before any rank returns
-    return ep
+        r.close_generation(t1 - t0, time.perf_counter() - t1)
+    return r.finish(runtime)
+
+
+# ---------------------------------------------------------------------------------------------- several runs at once
+SWEEP_FIELDS = ('seed', 'selection_method', 'save_dir')  # what the runs of one run_many may differ in
+
+
+class _HostStreams:
+    """One run's copy of the process-global numpy and torch generator states: restore() before a piece of the run's
+    host work, save() after it, so that the run draws exactly what it would draw alone."""
+
+    def save(self):
+        self.np_state, self.torch_state = np.random.get_state(), torch.get_rng_state()
+
+    def restore(self):
+        np.random.set_state(self.np_state)
+        torch.set_rng_state(self.torch_state)
+
+
+def check_sweep_args(args_list):
+    """The runs of a sweep share one population, so they may differ in SWEEP_FIELDS only; ValueError naming the first
+    other field that differs."""
+    if not args_list:
+        raise ValueError('run_many: no runs')
+    first = vars(args_list[0])
+    for i, a in enumerate(args_list[1:], 1):
+        va = vars(a)
+        for k in sorted(set(first) | set(va)):
+            if k in SWEEP_FIELDS:
+                continue
+            if k not in first or k not in va or first[k] != va[k]:
+                raise ValueError(f'run_many: run {i} differs from run 0 in {k!r} ({va.get(k)!r} != {first.get(k)!r}); '
+                                 f'the runs of a sweep may differ in {", ".join(SWEEP_FIELDS)} only')
+    dirs = [os.path.abspath(a.save_dir) for a in args_list]
+    if len(set(dirs)) != len(dirs):
+        raise ValueError('run_many: two runs share a save_dir')
+
+
+def tasks_per_run(args):
+    """The most tasks one run puts into a generation: the warm-up's weight grid or --num-tasks."""
+    grid = len(weight_grid(args.obj_num, args.delta_weight, args.min_weight, args.max_weight))
+    return max(grid, int(getattr(args, 'num_tasks', 0) or 0))
+
+
+def sweep_chunks(args_list, max_tasks=None, fits=None):
+    """Consecutive chunks of run indices, each a complete multi-run: the largest prefix of the remaining runs whose
+    tasks (tasks_per_run x runs) ``fits`` accepts (a host-only probe, MOPGPopulation.update_fits) and that stays
+    within max_tasks.  One run always forms a chunk (what a solo run would attempt)."""
+    per = tasks_per_run(args_list[0])
+    n = len(args_list)
+    cap = n
+    if max_tasks is not None:
+        if max_tasks < per:
+            raise ValueError(f'--max-tasks {max_tasks} is below the {per} tasks of one run')
+        cap = min(cap, max_tasks // per)
+    if fits is not None:
+        while cap > 1 and not fits(cap * per):
+            cap -= 1
+    return [list(range(i, min(i + cap, n))) for i in range(0, n, cap)]
+
+
+def run_many(args_list, device='cuda', rng='device', log=None, runtime=None, max_tasks=None, info=None):
+    """Several runs of the generation loop (one args object each, differing in seed, selection_method and save_dir
+    only) on ONE device population: per generation the runs' task batches are concatenated in run order, the runtime
+    is called once with the run index of every task (MOPGPopulation(run_seeds=...): a task resets from its own run's
+    tables; noise, permutations and the learning rate depend on the iteration alone, morl/mopg.py:96), and each run's
+    generation boundary then runs in run order.  Every run owns its numpy / torch global generator states
+    (_HostStreams) and writes the results tree run() alone writes.  Returns the runs' EPs.
+
+    log: None, one callable (each line prefixed with the run index) or a list of callables, one per run.
+    runtime: a factory (args, run_seeds) -> runtime (default MOPGPopulation on ``device``); a runtime must accept
+    run(..., log=[per-run callables], run_of_task=ids) and evaluate_samples(..., run_of_task=ids).  Its run() must
+    either leave the process-global numpy / torch streams alone or reseed them deterministically (a function of the
+    iteration alone) and say so in an attribute ``reseeds_global_streams``, a tuple out of ('numpy', 'torch'):
+    MOPGPopulation declares ('torch',) with rng='host'.  A runtime that merely draws from a global stream has no place
+    here: its draws would depend on which run's state happened to be installed.
+    max_tasks: most tasks of one launch; more runs are processed in consecutive chunks (sweep_chunks).
+    info: a dict that receives the chunking, the tasks per generation and the wall / MOPG / boundary seconds."""
+    args_list = list(args_list)
+    check_sweep_args(args_list)
+    if world()[1] > 1:
+        raise ValueError('run_many: a sweep runs on one rank (multi-GPU sweeps are not built)')
+    if log is None or isinstance(log, (list, tuple)):
+        logs = list(log) if log is not None else [None] * len(args_list)
+    else:
+        logs = [(lambda *m, i=i: log(f'[run {i}]', *m)) for i in range(len(args_list))]
+    if len(logs) != len(args_list):
+        raise ValueError(f'run_many: {len(logs)} logs for {len(args_list)} runs')
+    make = runtime
+    if make is None:
+        def make(a, run_seeds):
+            return MOPGPopulation(a, device=device, rng=rng, run_seeds=run_seeds)
+    fits = None
+    if runtime is None:
+        fits = lambda P: MOPGPopulation.update_fits(args_list[0], P, device)  # noqa: E731
+    chunks = sweep_chunks(args_list, max_tasks, fits)
+    t_wall = time.perf_counter()
+    rec = {'runs': len(args_list), 'tasks_per_run': tasks_per_run(args_list[0]), 'chunks': chunks, 'rl_s': 0.0,
+           'boundary_s': [0.0] * len(args_list), 'generations': []}
+    eps = [None] * len(args_list)
+    for chunk in chunks:
+        for i, ep in zip(chunk, _run_chunk([args_list[i] for i in chunk], [logs[i] for i in chunk], make, rec, chunk)):
+            eps[i] = ep
+    rec['wall_s'] = time.perf_counter() - t_wall
+    if info is not None:
+        info.update(rec)
+    return eps
+
+
+def _run_chunk(args_list, logs, make, rec, ids):
+    """One complete multi-run over args_list (run_many)."""
+    R = len(args_list)
+    runs, streams = [], [_HostStreams() for _ in range(R)]
+    rt = None
+    for a, lg, hs in zip(args_list, logs, streams):
+        runs.append(_Run(a, lg))  # seeds the global streams with the run's seed
+        if rt is None:
+            rt = make(args_list[0], [x.seed for x in args_list])
+        runs[-1].setup()
+        hs.save()
+    # warm-up: every run's policies drawn from its own streams, then ONE evaluation of all of them
+    samples, weights, rids = [], [], []
+    for r, (run, hs) in enumerate(zip(runs, streams)):
+        hs.restore()
+        smp, wb = run.warm_up_samples(rt)
+        hs.save()
+        samples += smp
+        weights += list(wb)
+        rids += [r] * len(smp)
+    objs = rt.evaluate_samples(samples, weights, run_of_task=np.asarray(rids, dtype=np.int32))
+    o = 0
+    for run, hs in zip(runs, streams):
+        n = len(run.elite_batch)
+        hs.restore()
+        run.warm_up_done(objs[o:o + n])
+        hs.save()
+        o += n
+    del samples
+    quiet = lambda *m: None  # noqa: E731
+    while not runs[0].done:
+        batches = []
+        for run, hs in zip(runs, streams):
+            hs.restore()
+            batches.append(run.tasks())
+            hs.save()
+        flat = [t for b in batches for t in b]
+        rids = np.asarray([r for r, b in enumerate(batches) for _ in b], dtype=np.int32)
+        t0 = time.perf_counter()
+        offspring = rt.run(flat, runs[0].iteration, runs[0].rl_num_updates, runs[0].start_time,
+                           log=[lg or quiet for lg in logs], run_of_task=rids)
+        t1 = time.perf_counter()
+        # a runtime that reseeds a global stream itself (--rng host: torch.manual_seed(j), morl/mopg.py:96) leaves it in
+        # the state every run would find after its own solo call: all runs continue from it
+        reseeded = getattr(rt, 'reseeds_global_streams', ())
+        for hs in streams:
+            if 'numpy' in reseeded:
+                hs.np_state = np.random.get_state()
+            if 'torch' in reseeded:
+                hs.torch_state = torch.get_rng_state()
+        host = []
+        o = 0
+        for run, hs, n in zip(runs, streams, [len(b) for b in batches]):
+            tb = time.perf_counter()
+            hs.restore()
+            run.boundary(offspring[o:o + n])
+            hs.save()
+            o += n
+            host.append(time.perf_counter() - tb)
+        rec['generations'].append({'iteration': runs[0].iteration, 'runs': ids, 'tasks': len(flat),
+                                   'rl_s': round(t1 - t0, 4), 'boundary_s': [round(h, 4) for h in host]})
+        del offspring, flat, batches  # (nothing else holds this generation's Tasks or offspring lists)
+        compact_snapshots()
+        rec['rl_s'] += t1 - t0
+        for run, h, i in zip(runs, host, ids):
+            tb = time.perf_counter()
+            run.close_generation(t1 - t0, h)  # (rl_s of a run's timing.json: the shared call's time)
+            rec['boundary_s'][i] += h + time.perf_counter() - tb
+    eps = []
+    for run, hs in zip(runs, streams):
+        hs.restore()
+        eps.append(run.finish(rt))
+        hs.save()
+    return eps
 
 
 def generation_record(save_dir, iteration, obj_num, ep, population, opt_graph, elite_batch, scalarization_batch,

@@ -35,7 +35,7 @@ import torch
 from . import envspec
 from ._lib import (ANY_MAX_ACT, ANY_MAX_OBJ, ANY_MAX_OBS, Dims, DstSpec, DummySpec, EnvSpec, EnvState, NormState,
                    PGMError, PPOHParams, RolloutBuf, check, launch_opts, lib, require_any_dims, require_categorical,
-                   require_dst_device, require_dummy_device)
+                   require_dst_device, require_dummy_device, require_runs)
 from .layout import ParamLayout
 
 F32, F64, I32 = torch.float32, torch.float64, torch.int32
@@ -72,7 +72,7 @@ class TaskBatch:
                  clip_param=0.2, ppo_epoch=10, num_mini_batch=32, value_loss_coef=0.5, entropy_coef=0.0,
                  max_grad_norm=0.5, adam_eps=1e-5, use_clipped_value_loss=True, device='cuda', capacity=None,
                  layernorm=False, host_env=None, device_env=False, *, max_steps=None, time_limit_is_bad=None,
-                 bound=None, R=None, any_dims=False, env_plugin=None):
+                 bound=None, R=None, any_dims=False, env_plugin=None, run_seeds=None):
         """device_env: run a discrete-action env on the device (Deep Sea Treasure: pgm_rollout_dst / pgm_eval_dst)
         instead of on the host; for such an env exactly one of host_env and device_env=True is given.  The SynthMO envs
         are device envs already: the flag changes nothing there.  max_steps / time_limit_is_bad: the device Deep Sea
@@ -85,7 +85,25 @@ class TaskBatch:
         third-party env (envspec.register_env) always runs on them.  env_plugin: a device env plug-in
         (envplug.EnvPlugin, or the path of its header): env_name is registered with the header's dims, the batch is a
         runtime-dim batch whose rollout and evaluation are the plug-in library's fused kernels, on the device envs'
-        schedule (overlapped evaluation included); R: reset-table entries per env (default envplug.DEFAULT_RESETS)."""
+        schedule (overlapped evaluation included); R: reset-table entries per env (default envplug.DEFAULT_RESETS).
+        run_seeds: a list of seeds makes the batch hold the tasks of several runs (a sweep): the reset tables are
+        stacked per run, task p resets from the block of run ``run_of_task[p]`` (set_runs) and env_reset / rollout /
+        evaluate go through the *_runs entry points; `seed` is then unused.  SynthMO device envs only."""
+        self.run_seeds = None
+        if run_seeds is not None:
+            self.run_seeds = [int(x) for x in run_seeds]
+            if not self.run_seeds:
+                raise PGMError('run_seeds=[]: a multi-run batch needs at least one seed')
+            for flag, on in (('host_env', host_env is not None), ('device_env', bool(device_env)),
+                             ('env_plugin', env_plugin is not None)):
+                if on:
+                    raise PGMError(f'run_seeds=... with {flag}=...: several runs share one population on the SynthMO '
+                                   f'device envs only (the reset tables of {flag} have another shape)')
+            sp_ = envspec.make_spec(env_name)
+            if sp_.get('native') == 'dummy' or sp_.get('discrete') or sp_.get('user'):
+                raise PGMError(f'run_seeds=... with {env_name}: several runs share one population on the SynthMO '
+                               f'device envs only (the MO-Dummy / Deep Sea Treasure reset tables are per family)')
+            require_runs()
         self.plugin = None
         if env_plugin is not None:
             from . import envplug
@@ -206,8 +224,15 @@ class TaskBatch:
         # spec constants + reset tables (fp64)
         self._spec_t = {k: torch.tensor(np.ascontiguousarray(sp[k]), dtype=F64, device=self.dev)
                         for k in ('d', 'U', 'c', 'V', 'ebase', 'ecoef', 'act_lo', 'act_hi') if k in sp}
-        self.s0_train = torch.tensor(envspec.reset_table(O, seed, N), dtype=F64, device=self.dev)
-        self.s0_eval = torch.tensor(envspec.reset_table(O, seed, eval_num), dtype=F64, device=self.dev)
+        if self.run_seeds is None:
+            self.s0_train = torch.tensor(envspec.reset_table(O, seed, N), dtype=F64, device=self.dev)
+            self.s0_eval = torch.tensor(envspec.reset_table(O, seed, eval_num), dtype=F64, device=self.dev)
+        else:  # [num_runs][N][O] / [num_runs][eval_num][O]: block r is run r's table; every task starts in run 0
+            self.s0_train = torch.tensor(np.stack([envspec.reset_table(O, sd, N) for sd in self.run_seeds]),
+                                         dtype=F64, device=self.dev)
+            self.s0_eval = torch.tensor(np.stack([envspec.reset_table(O, sd, eval_num) for sd in self.run_seeds]),
+                                        dtype=F64, device=self.dev)
+            self.run_of_task = torch.zeros(Pc, dtype=I32, device=self.dev)
         # policy + optimiser: one [3][Pc][L] region
         self._state = torch.zeros(3, Pc, L, dtype=F32, device=self.dev)
         z('adam_step', dt=I32)
@@ -464,6 +489,18 @@ class TaskBatch:
         if self.host_env is not None:
             self._host_views()
 
+    def set_runs(self, ids):
+        """run_of_task of the active tasks: ids[p] in [0, len(run_seeds)) is the run whose reset tables task p uses.
+        Checked here (the kernels trust the device copy), then uploaded."""
+        if self.run_seeds is None:
+            raise PGMError('set_runs: this batch was built without run_seeds=...')
+        ids = np.asarray(ids)
+        if ids.ndim != 1 or len(ids) != self.P:
+            raise PGMError(f'set_runs: {ids.shape} run ids for {self.P} active tasks (one id per task)')
+        if len(ids) and (not np.issubdtype(ids.dtype, np.integer) or ids.min() < 0 or ids.max() >= len(self.run_seeds)):
+            raise PGMError(f'set_runs: run ids must be integers in [0, {len(self.run_seeds)}), got {ids.tolist()}')
+        self.run_of_task[:self.P].copy_(torch.from_numpy(ids.astype(np.int32)))
+
     @property
     def state(self):
         """[3][P][L] view of the active slots (params | exp_avg | exp_avg_sq); strided when P < capacity."""
@@ -561,8 +598,13 @@ class TaskBatch:
                   'pgm_env_ingest')
             return self.obs[:, 0]
         out = torch.empty(self.P, self.N, self.O, dtype=F32, device=self.dev)
-        check(lib().pgm_env_reset(C.byref(self.dims), C.byref(self.c_spec), C.byref(self.c_state),
-                                  C.byref(self.c_norm), _ptr(out), _stream()), 'pgm_env_reset')
+        if self.run_seeds is not None:
+            check(lib().pgm_env_reset_runs(C.byref(self.dims), C.byref(self.c_spec), C.byref(self.c_state),
+                                           C.byref(self.c_norm), _ptr(self.run_of_task), len(self.run_seeds),
+                                           _ptr(out), _stream()), 'pgm_env_reset_runs')
+        else:
+            check(lib().pgm_env_reset(C.byref(self.dims), C.byref(self.c_spec), C.byref(self.c_state),
+                                      C.byref(self.c_norm), _ptr(out), _stream()), 'pgm_env_reset')
         self.obs[:, 0].copy_(out)
         self.masks[:, 0] = 1.0
         self.bad_masks[:, 0] = 1.0
@@ -575,6 +617,9 @@ class TaskBatch:
         if self.any_dims:
             raise PGMError('env_step: this batch runs on the runtime-dim kernels, which are host-stepped only: the '
                            'environments are stepped inside rollout(), there is no device env to step')
+        if self.run_seeds is not None:
+            raise PGMError('env_step: a multi-run batch (run_seeds=...) has no single-step kernel that takes the reset '
+                           'rows per task; the envs are stepped inside rollout()')
         if self.host_env is not None:
             raise PGMError('env_step: this batch is in host-env mode (TaskBatch(host_env=...)): the environments are '
                            'stepped on the host inside rollout(), there is no device env to step')
@@ -640,6 +685,12 @@ class TaskBatch:
                                           C.byref(self.c_state), _ptr(self.episode), C.byref(self.c_norm),
                                           C.byref(self.c_rb), _ptr(nz), C.c_uint64(seed), int(carry), _stream()),
                   'pgm_rollout_dummy')
+            return
+        if self.run_seeds is not None:
+            check(lib().pgm_rollout_runs(C.byref(self.dims), _ptr(self.params), C.byref(self.c_spec),
+                                         C.byref(self.c_state), C.byref(self.c_norm), C.byref(self.c_rb), _ptr(nz),
+                                         C.c_uint64(seed), int(carry), _ptr(self.run_of_task), len(self.run_seeds),
+                                         C.byref(launch_opts()), _stream()), 'pgm_rollout_runs')
             return
         check(lib().pgm_rollout(C.byref(self.dims), _ptr(self.params), C.byref(self.c_spec), C.byref(self.c_state),
                                 C.byref(self.c_norm), C.byref(self.c_rb), _ptr(nz), C.c_uint64(seed),
@@ -744,6 +795,12 @@ class TaskBatch:
             check(lib().pgm_eval_dummy(C.byref(self.dims), _ptr(self.params), C.byref(self.c_dummy_eval), _ptr(mean),
                                        _ptr(var), self.eval_num, int(self.use_ob_rms), int(self.raw), self.gamma,
                                        _ptr(out), _stream()), 'pgm_eval_dummy')
+            return out
+        if self.run_seeds is not None:
+            check(lib().pgm_eval_runs(C.byref(self.dims), _ptr(self.params), C.byref(self.c_spec), _ptr(mean),
+                                      _ptr(var), _ptr(self.s0_eval), self.eval_num, int(self.use_ob_rms),
+                                      int(self.raw), self.gamma, _ptr(out), _ptr(self.run_of_task),
+                                      len(self.run_seeds), C.byref(launch_opts()), _stream()), 'pgm_eval_runs')
             return out
         check(lib().pgm_eval(C.byref(self.dims), _ptr(self.params), C.byref(self.c_spec), _ptr(mean), _ptr(var),
                              _ptr(self.s0_eval), self.eval_num, int(self.use_ob_rms), int(self.raw), self.gamma,

@@ -336,7 +336,30 @@ int pgm_eval_runs(const pgm_dims* d, const float* params, const pgm_env_spec* sp
                   double gamma, double* objs_out, const int32_t* run_of_task, int32_t num_runs,
                   const pgm_launch_opts* opts, pgm_stream_t stream);
 
-/* ---- Host-stepped environments (from minor 1).  The environments run on the host; policy, VecNormalize
+/* ---- Per-task PPO settings (discovered by the presence of the symbol pgm_ppo_update_tasks; no feature bit, no version
+ * change).  The runs of a sweep that differ in a hyper-parameter share one population: task p takes the four loss /
+ * clip settings from hp_task[p] and its GAE lambda from lam_task[p]; lr is [P] already.  Everything else comes from
+ * the shared arguments: the Adam constants, ppo_epoch, num_mini_batch, use_clipped_value_loss, gamma (which also
+ * enters the rollout's return normalisation and the evaluation discount) and the shapes.  The kernel selection rule,
+ * pgm_ppo_update_variant and pgm_ppo_update_workspace_bytes are pgm_ppo_update's: none of them reads the four fields.
+ * The kernels are the TASKS instantiations of the ones pgm_ppo_update / pgm_gae launch: a workgroup serves one task
+ * and replaces the launch's values by one wave-uniform 16-byte (4-byte) load before anything reads them; with every
+ * entry equal to the shared value the outputs are pgm_ppo_update's / pgm_gae's bit for bit.
+ * Validation: every check of the entry point each extends, in its order and with its strings; then a NULL table is
+ * PGM_E_INVALID_ARG naming the _tasks entry point.  The tables are DEVICE memory ([P], the pgm_task_hparams array
+ * 16-byte aligned) and are not read on the host: the caller guarantees finite values, clip_param > 0,
+ * max_grad_norm > 0 and 0 <= lam <= 1. */
+typedef struct pgm_task_hparams {
+    float clip_param, value_loss_coef, entropy_coef, max_grad_norm;
+} pgm_task_hparams;
+int pgm_ppo_update_tasks(const pgm_dims* d, const pgm_ppo_hparams* hp, const pgm_task_hparams* hp_task, float* params,
+                         float* adam_m, float* adam_v, int32_t* adam_step, const float* lr, const int32_t* perms,
+                         const pgm_rollout_buf* rb, float* stats, void* workspace, const pgm_launch_opts* opts,
+                         pgm_stream_t stream);
+int pgm_gae_tasks(const pgm_dims* d, const pgm_rollout_buf* rb, float gamma, const float* lam_task, int32_t use_gae,
+                  int32_t use_proper_time_limits, pgm_stream_t stream);
+
+/* ---- Host-stepped environments (from minor 1). The environments run on the host; policy, VecNormalize
  * statistics, rollout storage and the PPO update stay on the device.  One rollout step t is
  *     pgm_rollout_act(t) -> copy action_out to the host -> envs.step(actions) -> copy the transition to the device
  *     -> pgm_env_ingest(t)

@@ -169,8 +169,15 @@ _SIGS = {
                                    C.POINTER(RolloutBuf), P_, C.c_uint64, I32, P_, I32, C.POINTER(LaunchOpts), P_]),
     'pgm_eval_runs': (C.c_int, [C.POINTER(Dims), P_, C.POINTER(EnvSpec), P_, P_, P_, I32, I32, I32, F64, P_, P_, I32,
                                 C.POINTER(LaunchOpts), P_]),
+    # per-task PPO settings of a hyper-parameter grid (no feature bit: discovered by the symbol pgm_ppo_update_tasks);
+    # hp_task (device pgm_task_hparams [P]) sits after hp, lam_task (device float [P]) in the place of lam
+    'pgm_ppo_update_tasks': (C.c_int, [C.POINTER(Dims), C.POINTER(PPOHParams), P_, P_, P_, P_, P_, P_, P_,
+                                       C.POINTER(RolloutBuf), P_, P_, C.POINTER(LaunchOpts), P_]),
+    'pgm_gae_tasks': (C.c_int, [C.POINTER(Dims), C.POINTER(RolloutBuf), F32, P_, I32, I32, P_]),
 }
 RUNS_SYMBOLS = ('pgm_env_reset_runs', 'pgm_rollout_runs', 'pgm_eval_runs')
+TASKS_SYMBOLS = ('pgm_ppo_update_tasks', 'pgm_gae_tasks')
+TASK_HPARAM_FIELDS = ('clip_param', 'value_loss_coef', 'entropy_coef', 'max_grad_norm')  # pgm_task_hparams, in order
 # the symbols a library of the same ABI version and minor may lack: discovered through pgm_abi_features
 FEATURE_CATEGORICAL = 1
 FEATURE_DST_DEVICE = 2
@@ -205,8 +212,8 @@ def _load(path):
             raise PGMError(f'{path} not built; run `python -m pgmorl_amd.build` (hipcc, gfx950)')
         h = C.CDLL(path)
         for name, (res, args) in _SIGS.items():
-            if (name in _FEATURE_SYMBOLS or name in RUNS_SYMBOLS) and not hasattr(h, name):
-                continue  # an older library of this ABI: features() / has_runs() report what is missing
+            if (name in _FEATURE_SYMBOLS or name in RUNS_SYMBOLS or name in TASKS_SYMBOLS) and not hasattr(h, name):
+                continue  # an older library of this ABI: features() / has_runs() / has_tasks() report what is missing
             f = getattr(h, name)
             f.restype, f.argtypes = res, args
         if h.pgm_abi_version() != PGM_ABI_VERSION:
@@ -290,6 +297,18 @@ def require_runs():
     if not has_runs():
         raise PGMError('this libpgm.so has no pgm_rollout_runs (the per-run reset tables of a batched sweep); '
                        'rebuild it with `python -m pgmorl_amd.build`')
+
+
+def has_tasks():
+    """True if the library has the *_tasks entry points (per-task PPO settings): the presence of the symbol
+    pgm_ppo_update_tasks, as include/pgm_abi.h documents (there is no feature bit)."""
+    return hasattr(lib(), 'pgm_ppo_update_tasks')
+
+
+def require_tasks():
+    if not has_tasks():
+        raise PGMError('this libpgm.so has no pgm_ppo_update_tasks (the per-task PPO settings of a hyper-parameter '
+                       'grid); rebuild it with `python -m pgmorl_amd.build`')
 
 
 def param_layout_cat(O, A, K, H=64):

@@ -3,6 +3,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <type_traits>
+
 #include "../../include/pgm_abi.h"
 
 namespace pgm {
@@ -124,6 +126,32 @@ __device__ __forceinline__ void dbg_delay(const DbgDelay& d, int nstep, int wher
         const unsigned long long t0 = __builtin_amdgcn_s_memtime();
         while (__builtin_amdgcn_s_memtime() - t0 < (unsigned long long)d.cycles) __builtin_amdgcn_s_sleep(8);
     }
+}
+
+// The *_tasks entry points (runs of a sweep that differ in a hyper-parameter): task p takes clip_param,
+// value_loss_coef, entropy_coef and max_grad_norm from hp_task[p].  A kernel instantiated with TASKS takes its argument
+// block with the table pointer appended and overwrites the four fields of its by-value hp once, before anything reads
+// them; the TASKS = false instantiation is the kernel as it was (the argument block included).  A workgroup serves
+// one task in every update kernel, so p is wave-uniform and the read is one scalar 16-byte load.
+template <class Base>
+struct TaskArgs : Base {
+    const pgm_task_hparams* hp_task;  // [P], device, 16-byte aligned
+};
+template <class Base, bool TASKS>
+using TaskArgsT = std::conditional_t<TASKS, TaskArgs<Base>, Base>;
+template <class Base>
+inline TaskArgs<Base> with_task_table(const Base& a, const pgm_task_hparams* hp_task) {
+    TaskArgs<Base> r;
+    static_cast<Base&>(r) = a;
+    r.hp_task = hp_task;
+    return r;
+}
+__device__ __forceinline__ void take_task_hparams(pgm_ppo_hparams& hp, const pgm_task_hparams* hp_task, int p) {
+    const pgm_task_hparams th = hp_task[p];
+    hp.clip_param = th.clip_param;
+    hp.value_loss_coef = th.value_loss_coef;
+    hp.entropy_coef = th.entropy_coef;
+    hp.max_grad_norm = th.max_grad_norm;
 }
 
 // ---------------------------------------------------------------- device helpers

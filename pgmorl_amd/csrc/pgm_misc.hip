@@ -54,9 +54,16 @@ __device__ __forceinline__ void gae_coef(const GaeArgs& a, const float* rew, con
     }
 }
 
-__global__ __launch_bounds__(GT) void gae_kernel(GaeArgs a) {
+// TASKS (pgm_gae_tasks): the argument block with the per-task lambda table appended; task p's entry replaces a.lam
+// before anything reads it
+struct GaeTaskArgs : GaeArgs {
+    const float* lam_task;  // [P], device
+};
+template <bool TASKS>
+__global__ __launch_bounds__(GT) void gae_kernel(std::conditional_t<TASKS, GaeTaskArgs, GaeArgs> a) {
     __shared__ double yin[GT];
     const int p = blockIdx.x, t = threadIdx.x, N = a.N, T = a.T, K = a.K;
+    if constexpr (TASKS) a.lam = a.lam_task[p];
     const int lanes = N * K;
     const int C = GT / lanes;                 // chunks per lane (>= 1: N*K <= 64 checked on host)
     const int len = (T + C - 1) / C;
@@ -202,8 +209,9 @@ using namespace pgm;
 
 extern "C" {
 
-int pgm_gae(const pgm_dims* d, const pgm_rollout_buf* rb, float gamma, float lam, int32_t use_gae,
-            int32_t use_proper_time_limits, pgm_stream_t stream) {
+// pgm_gae (tasks = false) and pgm_gae_tasks: one body, the table check last
+static int gae_entry(const pgm_dims* d, const pgm_rollout_buf* rb, float gamma, float lam, const float* lam_task,
+                     bool tasks, int32_t use_gae, int32_t use_proper_time_limits, pgm_stream_t stream) {
     if (!d || !rb || !rb->rewards || !rb->values || !rb->masks || !rb->bad_masks || !rb->returns) {
         set_error("pgm_gae: null pointer");
         return PGM_E_INVALID_ARG;
@@ -214,8 +222,29 @@ int pgm_gae(const pgm_dims* d, const pgm_rollout_buf* rb, float gamma, float lam
     }
     GaeArgs a{d->N, d->T, d->K, rb->rewards, rb->values, rb->masks, rb->bad_masks, rb->returns, gamma, lam,
               use_gae, use_proper_time_limits};
-    hipLaunchKernelGGL(gae_kernel, dim3(d->P), dim3(GT), 0, (hipStream_t)stream, a);
+    if (tasks) {
+        if (!lam_task) {
+            set_error("pgm_gae_tasks: null lam_task");
+            return PGM_E_INVALID_ARG;
+        }
+        GaeTaskArgs ta;
+        static_cast<GaeArgs&>(ta) = a;
+        ta.lam_task = lam_task;
+        hipLaunchKernelGGL(gae_kernel<true>, dim3(d->P), dim3(GT), 0, (hipStream_t)stream, ta);
+        return launch_status("pgm_gae");
+    }
+    hipLaunchKernelGGL(gae_kernel<false>, dim3(d->P), dim3(GT), 0, (hipStream_t)stream, a);
     return launch_status("pgm_gae");
+}
+
+int pgm_gae(const pgm_dims* d, const pgm_rollout_buf* rb, float gamma, float lam, int32_t use_gae,
+            int32_t use_proper_time_limits, pgm_stream_t stream) {
+    return gae_entry(d, rb, gamma, lam, nullptr, false, use_gae, use_proper_time_limits, stream);
+}
+
+int pgm_gae_tasks(const pgm_dims* d, const pgm_rollout_buf* rb, float gamma, const float* lam_task, int32_t use_gae,
+                  int32_t use_proper_time_limits, pgm_stream_t stream) {
+    return gae_entry(d, rb, gamma, 0.f, lam_task, true, use_gae, use_proper_time_limits, stream);
 }
 
 int pgm_adv_normalize(const pgm_dims* d, const pgm_rollout_buf* rb, const double* weights,

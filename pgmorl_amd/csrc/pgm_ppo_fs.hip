@@ -921,9 +921,9 @@ __device__ __forceinline__ void fs_update_tower(const MArgs& a, const int p, con
     }
 }
 
-template <int O, int A, int K, int NS, int R>
+template <int O, int A, int K, int NS, int R, bool TASKS>
 // R = 3: held to 256 registers, so that two workgroups share a CU (fs_choose_ns dual; R = 2 fits by itself)
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(R == 3 ? 2 : 1))) void ppo_update_fs_kernel(MArgs a) {
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(R == 3 ? 2 : 1))) void ppo_update_fs_kernel(TaskArgsT<MArgs, TASKS> a) {
     // block map: groups of 16 NS blocks for 8 tasks; block r holds part (r >> 4) % NS of tower (r >> 3) & 1 of task
     // 8 G + (r & 7), so every workgroup of a task shares blocks b, b + 8, ... (one XCD: speed only)
     const int bx = (int)blockIdx.x;
@@ -931,6 +931,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(R == 3 ? 2 
     const int p = 8 * (bx / (16 * NS)) + (bx & 7);
     const int hs = j16 >> 1, m = j16 & 1;
     if (p >= a.P) return;
+    if constexpr (TASKS) take_task_hparams(a.hp, a.hp_task, p);
     if constexpr (NS == 6 && R == 3) {
         // the part's own tiles (as fs_update_tower deals them): 3 or 2
         const int mb = a.T * a.N / a.hp.num_mini_batch, ntl = mb >> 4, tb0 = ntl / NS;
@@ -948,15 +949,17 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(R == 3 ? 2 
 
 // op 0: launch (dual: two workgroups per CU); op 1: 1 if two workgroups of this kernel fit one CU (LDS and registers),
 // else 0; op 2: 1 if one workgroup's LDS fits a CU (160 KiB), else 0
-template <int O, int A, int K, int NS, int R>
-static int launch_fs_k(const pgm_dims* d, const MArgs& a, bool dual, int op, hipStream_t stream) {
+// (TASKS: the per-task-table twin.  fs_choose_ns asks the TASKS = false kernels, so the selection rule is one; the
+// launch checks the co-residency of the kernel it launches)
+template <int O, int A, int K, int NS, int R, bool TASKS>
+static int launch_fs_k(const pgm_dims* d, const TaskArgsT<MArgs, TASKS>& a, bool dual, int op, hipStream_t stream) {
     const size_t smem = fs_smem_bytes<O, A, K, R>(dual || op == 1);
     if (op == 2) return smem <= 160 * 1024 ? 1 : 0;
     if (smem > 160 * 1024) {
         set_error("pgm_ppo_update (fs): LDS %zu bytes exceeds 160 KiB", smem);
         return op == 1 ? 0 : PGM_E_UNSUPPORTED;
     }
-    auto kern = ppo_update_fs_kernel<O, A, K, NS, R>;
+    auto kern = ppo_update_fs_kernel<O, A, K, NS, R, TASKS>;
     hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
     if (e != hipSuccess) return op == 1 ? 0 : hip_fail(e, "pgm_ppo_update (fs)");
     if (op == 1) {
@@ -976,7 +979,8 @@ static int launch_fs_k(const pgm_dims* d, const MArgs& a, bool dual, int op, hip
     return launch_status("pgm_ppo_update (fs)");
 }
 
-int ppo_update_fs_op(const pgm_dims* d, const MArgs& a, int ns, bool dual, int op, hipStream_t stream);
+int ppo_update_fs_op(const pgm_dims* d, const MArgs& a, int ns, bool dual, int op, hipStream_t stream,
+                     const pgm_task_hparams* hp_task = nullptr);
 
 // NS parts per tower for this launch: the workspace cap, the device's CUs, mb divisible into 16-row tiles of at most
 // 8 per part; 0 = the feature-split update does not apply.  *dual = 1: the grid (16 NS ceil(P/8) workgroups) exceeds
@@ -1013,11 +1017,15 @@ int fs_choose_ns(const pgm_dims* d, int mb, bool dual_ok, int* dual) {
 }
 
 template <int O, int A, int K, int NS>
-static int launch_fs_ns(const pgm_dims* d, const MArgs& a, int R, bool dual, int op, hipStream_t stream) {
+static int launch_fs_ns(const pgm_dims* d, const MArgs& a, int R, bool dual, int op, hipStream_t stream,
+                        const pgm_task_hparams* hp_task) {
     // minibatches of 64 / 128 / 256 / 512 rows (N = 1 / 2 / 4 / 8 at T = 2048, M = 32): 16 NS R = mb
     auto one = [&](auto rc) -> int {
         constexpr int RR = decltype(rc)::value, MB = 16 * NS * RR;
-        if constexpr (fs_built(NS, RR)) return launch_fs_k<O, A, K, NS, RR>(d, a, dual, op, stream);
+        if constexpr (fs_built(NS, RR)) {
+            if (hp_task) return launch_fs_k<O, A, K, NS, RR, true>(d, with_task_table(a, hp_task), dual, op, stream);
+            return launch_fs_k<O, A, K, NS, RR, false>(d, a, dual, op, stream);
+        }
         set_error("pgm_ppo_update (fs): minibatch of %d rows unsupported", MB);
         return PGM_E_UNSUPPORTED;
     };
@@ -1033,10 +1041,12 @@ static int launch_fs_ns(const pgm_dims* d, const MArgs& a, int R, bool dual, int
 }
 
 // called by pgm_ppo_mfma.hip's launcher after the sample table is packed
-int ppo_update_fs(const pgm_dims* d, const MArgs& a, int ns, bool dual, hipStream_t stream) {
-    return ppo_update_fs_op(d, a, ns, dual, 0, stream);
+int ppo_update_fs(const pgm_dims* d, const MArgs& a, int ns, bool dual, hipStream_t stream,
+                  const pgm_task_hparams* hp_task) {
+    return ppo_update_fs_op(d, a, ns, dual, 0, stream, hp_task);
 }
-int ppo_update_fs_op(const pgm_dims* d, const MArgs& a, int ns, bool dual, int op, hipStream_t stream) {
+int ppo_update_fs_op(const pgm_dims* d, const MArgs& a, int ns, bool dual, int op, hipStream_t stream,
+                     const pgm_task_hparams* hp_task) {
     const int mb = d->T * d->N / a.hp.num_mini_batch;
     const int R = fs_tiles(mb, ns);
     return dispatch_dims(d->O, d->A, d->K, "pgm_ppo_update (fs)", [&](auto o, auto aa, auto k) -> int {
@@ -1050,11 +1060,11 @@ int ppo_update_fs_op(const pgm_dims* d, const MArgs& a, int ns, bool dual, int o
             return op != 0 ? 0 : PGM_E_UNSUPPORTED;
         } else {
             switch (ns) {
-                case 2: return launch_fs_ns<O, A, K, 2>(d, a, R, dual, op, stream);
-                case 4: return launch_fs_ns<O, A, K, 4>(d, a, R, dual, op, stream);
-                case 6: return launch_fs_ns<O, A, K, 6>(d, a, R, dual, op, stream);
-                case 8: return launch_fs_ns<O, A, K, 8>(d, a, R, dual, op, stream);
-                case 16: return launch_fs_ns<O, A, K, 16>(d, a, R, dual, op, stream);
+                case 2: return launch_fs_ns<O, A, K, 2>(d, a, R, dual, op, stream, hp_task);
+                case 4: return launch_fs_ns<O, A, K, 4>(d, a, R, dual, op, stream, hp_task);
+                case 6: return launch_fs_ns<O, A, K, 6>(d, a, R, dual, op, stream, hp_task);
+                case 8: return launch_fs_ns<O, A, K, 8>(d, a, R, dual, op, stream, hp_task);
+                case 16: return launch_fs_ns<O, A, K, 16>(d, a, R, dual, op, stream, hp_task);
             }
             set_error("pgm_ppo_update (fs): NS=%d unsupported", ns);
             return PGM_E_UNSUPPORTED;

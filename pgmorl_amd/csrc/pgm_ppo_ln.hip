@@ -124,8 +124,8 @@ __device__ __forceinline__ void ln_backward_tile(f32x16 (&dh)[2], const f32x16 (
     }
 }
 
-template <int O, int A, int K>
-__global__ __launch_bounds__(MT) void ppo_update_ln_kernel(LnArgs a) {
+template <int O, int A, int K, bool TASKS>
+__global__ __launch_bounds__(MT) void ppo_update_ln_kernel(TaskArgsT<LnArgs, TASKS> a) {
     extern __shared__ __attribute__((aligned(16))) char smem_raw[];
     using Sm = LnSmem<O, A, K>;
     auto& S = *reinterpret_cast<Sm*>(smem_raw);
@@ -137,7 +137,8 @@ __global__ __launch_bounds__(MT) void ppo_update_ln_kernel(LnArgs a) {
     const int t = threadIdx.x, w = t >> 6, l = t & 63, h = l >> 5, c = l & 31;
     int p, m;
     if (!tower_block(a.P, p, m)) return;
-    const TowerTask<LnArgs> k(a, p, m, O, A, K);
+    if constexpr (TASKS) take_task_hparams(a.hp, a.hp_task, p);
+    const TowerTask<TaskArgsT<LnArgs, TASKS>> k(a, p, m, O, A, K);
     const int NQ = m == 0 ? K : A;
 
     auto& W = S.Pm;
@@ -264,7 +265,7 @@ int describe_update_ln(char* buf, int n) {
 
 int ppo_update_ln(const pgm_dims* d, const pgm_ppo_hparams* hp, float* params, float* adam_m, float* adam_v,
                   int32_t* adam_step, const float* lr, const int32_t* perms, const pgm_rollout_buf* rb, float* stats,
-                  void* workspace, hipStream_t stream) {
+                  void* workspace, hipStream_t stream, const pgm_task_hparams* hp_task) {
     if (!workspace) {
         set_error("pgm_ppo_update: the LayerNorm update needs the workspace (pgm_ppo_update_workspace_bytes)");
         return PGM_E_INVALID_ARG;
@@ -278,10 +279,13 @@ int ppo_update_ln(const pgm_dims* d, const pgm_ppo_hparams* hp, float* params, f
             set_error("pgm_ppo_update: LayerNorm towers need obs_dim <= 32 (got %d)", O);
             return PGM_E_UNSUPPORTED;
         } else {
-            return launch_tower_update<sizeof(LnSmem<O, A, K>)>(
-                ppo_update_ln_kernel<O, A, K>, a, stream, "pgm_ppo_update",
-                "pgm_ppo_update: the LayerNorm update runs one workgroup per tower and needs 2 P = %d <= %d "
-                "CUs; shard the tasks over more GPUs");
+            const char* need = "pgm_ppo_update: the LayerNorm update runs one workgroup per tower and needs 2 P = %d "
+                               "<= %d CUs; shard the tasks over more GPUs";
+            if (hp_task)
+                return launch_tower_update<sizeof(LnSmem<O, A, K>)>(
+                    ppo_update_ln_kernel<O, A, K, true>, with_task_table(a, hp_task), stream, "pgm_ppo_update", need);
+            return launch_tower_update<sizeof(LnSmem<O, A, K>)>(ppo_update_ln_kernel<O, A, K, false>, a, stream,
+                                                                "pgm_ppo_update", need);
         }
     });
 }

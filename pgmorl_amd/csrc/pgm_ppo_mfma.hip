@@ -143,8 +143,8 @@ using MSmem = MSmemT<O, A, K, SPLIT, nbuf<O, A, K, SPLIT>()>;
 // tagged granules (both compute half0 + half1 in that order, so their Adam steps stay bitwise identical).
 // ONE (MODE 2, mb = 256): every wave owns exactly one 32-row tile of one pass per minibatch; the pass and tile
 // loops are straight-line so the gradient accumulators are not loop-carried
-template <int O, int A, int K, int MODE, bool ONE>
-__global__ __launch_bounds__(MT) void ppo_update_mfma_kernel(MArgs a) {
+template <int O, int A, int K, int MODE, bool ONE, bool TASKS>
+__global__ __launch_bounds__(MT) void ppo_update_mfma_kernel(TaskArgsT<MArgs, TASKS> a) {
     constexpr bool SPLIT = MODE >= 1;
     constexpr int NS = MODE == 2 ? 2 : 1;  // workgroups per tower
     extern __shared__ __attribute__((aligned(16))) char smem_raw[];
@@ -173,6 +173,7 @@ __global__ __launch_bounds__(MT) void ppo_update_mfma_kernel(MArgs a) {
     const int p = MODE == 2 ? 8 * (bx >> 5) + (bx & 7) : SPLIT ? (bx >> 1) : bx;
     const int hs = MODE == 2 ? (bx >> 4) & 1 : 0;  // half of the minibatch rows
     if (p >= a.P) return;
+    if constexpr (TASKS) take_task_hparams(a.hp, a.hp_task, p);
     const int m = MODE == 2 ? (bx >> 3) & 1 : SPLIT ? (bx & 1) : (w & 1);  // tower of this wave
     const int sh = SPLIT ? w : (w >> 1);                      // wave index within the tower
     const int NQ = m == 0 ? K : A;
@@ -984,8 +985,8 @@ using T16Smem = T16SmemT<O, A, K, W, t16_nbuf<O, A, K, W>(), t16_nimg<O, A, K, W
 // ONE: the launcher checked mb == NS * W * 16 (every wave owns exactly one tile of one pass per minibatch), so
 // the pass and tile loops are straight-line and the gradient accumulators are no longer loop-carried: they go
 // live at their first MFMA instead of spanning the whole tile (W = 8: no spills)
-template <int O, int A, int K, int NS, int W, bool ONE>
-__global__ __launch_bounds__(64 * W) void ppo_update_t16_kernel(MArgs a) {
+template <int O, int A, int K, int NS, int W, bool ONE, bool TASKS>
+__global__ __launch_bounds__(64 * W) void ppo_update_t16_kernel(TaskArgsT<MArgs, TASKS> a) {
     static_assert(O <= 32, "two 16-feature blocks of layer-1 inputs");
     using Sm = T16Smem<O, A, K, W>;
     extern __shared__ __attribute__((aligned(16))) char smem_raw[];
@@ -1014,6 +1015,7 @@ __global__ __launch_bounds__(64 * W) void ppo_update_t16_kernel(MArgs a) {
     const int p = 8 * (bx / (16 * NS)) + (bx & 7);
     const int hs = j16 >> 1, m = j16 & 1;
     if (p >= a.P) return;
+    if constexpr (TASKS) take_task_hparams(a.hp, a.hp_task, p);
     const int NQ = m == 0 ? K : A;
     const int N = a.N, T = a.T, B = T * N;
     const int E = a.hp.ppo_epoch, M = a.hp.num_mini_batch;
@@ -1705,8 +1707,8 @@ PGM_UNROLL(ONE ? PGM_U16 : 4)
     }
 }
 
-template <int O, int A, int K, int NS, int W, bool ONE>
-static int launch_t16_k(const pgm_dims* d, const MArgs& a, hipStream_t stream) {
+template <int O, int A, int K, int NS, int W, bool ONE, bool TASKS>
+static int launch_t16_k(const pgm_dims* d, const TaskArgsT<MArgs, TASKS>& a, hipStream_t stream) {
     using Sm = T16Smem<O, A, K, W>;
     const size_t smem = sizeof(Sm);
     if (smem > 160 * 1024) {
@@ -1714,7 +1716,7 @@ static int launch_t16_k(const pgm_dims* d, const MArgs& a, hipStream_t stream) {
         return PGM_E_UNSUPPORTED;
     }
     static_assert(sizeof(Sm) > 80 * 1024, "residency argument (one workgroup per CU) needs > 80 KiB LDS");
-    auto kern = ppo_update_t16_kernel<O, A, K, NS, W, ONE>;
+    auto kern = ppo_update_t16_kernel<O, A, K, NS, W, ONE, TASKS>;
     const int grid = t16_grid(d->P, NS);
     const size_t zb = ppo_flag_bytes(d->P) + ppo_xbuf_bytes(d, NS);
     if (int rc = prepare_update_launch((const void*)kern, 64 * W, smem, grid, a.ws, zb, stream, "pgm_ppo_update"))
@@ -1724,23 +1726,28 @@ static int launch_t16_k(const pgm_dims* d, const MArgs& a, hipStream_t stream) {
 }
 
 template <int O, int A, int K, int NS, int W>
-int launch_t16(const pgm_dims* d, const MArgs& a, hipStream_t stream) {
+int launch_t16(const pgm_dims* d, const MArgs& a, hipStream_t stream, const pgm_task_hparams* hp_task) {
     const int mb = d->T * d->N / a.hp.num_mini_batch;
-    if (mb == NS * W * T16) return launch_t16_k<O, A, K, NS, W, true>(d, a, stream);
-    return launch_t16_k<O, A, K, NS, W, false>(d, a, stream);
+    if (hp_task) {
+        const auto ta = with_task_table(a, hp_task);
+        if (mb == NS * W * T16) return launch_t16_k<O, A, K, NS, W, true, true>(d, ta, stream);
+        return launch_t16_k<O, A, K, NS, W, false, true>(d, ta, stream);
+    }
+    if (mb == NS * W * T16) return launch_t16_k<O, A, K, NS, W, true, false>(d, a, stream);
+    return launch_t16_k<O, A, K, NS, W, false, false>(d, a, stream);
 }
 
 static int device_cus() { return device_cu_count(); }
 
-template <int O, int A, int K, int MODE, bool ONE>
-int launch_mode_k(const pgm_dims* d, const MArgs& a, hipStream_t stream) {
+template <int O, int A, int K, int MODE, bool ONE, bool TASKS>
+int launch_mode_k(const pgm_dims* d, const TaskArgsT<MArgs, TASKS>& a, hipStream_t stream) {
     constexpr bool SPLIT = MODE >= 1;
     const size_t smem = sizeof(MSmem<O, A, K, SPLIT>);
     if (smem > 160 * 1024) {
         set_error("pgm_ppo_update: LDS image %zu bytes exceeds 160 KiB", smem);
         return PGM_E_UNSUPPORTED;
     }
-    auto kern = ppo_update_mfma_kernel<O, A, K, MODE, ONE>;
+    auto kern = ppo_update_mfma_kernel<O, A, K, MODE, ONE, TASKS>;
     // norm granules, timeout flag (and MODE 2: the exchange slots) start at tag 0; MODE 0 resets the flag
     // word too, so word 2P always reports THIS call
     const int grid = MODE == 2 ? mode2_grid(d->P) : SPLIT ? 2 * d->P : d->P;
@@ -1754,17 +1761,21 @@ int launch_mode_k(const pgm_dims* d, const MArgs& a, hipStream_t stream) {
 }
 
 template <int O, int A, int K, int MODE>
-int launch_mode(const pgm_dims* d, const MArgs& a, hipStream_t stream) {
+int launch_mode(const pgm_dims* d, const MArgs& a, hipStream_t stream, const pgm_task_hparams* hp_task) {
     using Sm = MSmem<O, A, K, true>;
     if constexpr (MODE == 2) {  // 2 workgroups x 4 waves x one 32-row tile = the minibatch, in one pass
-        if (d->T * d->N / a.hp.num_mini_batch == 2 * 4 * TS && Sm::SBk >= 4 * TS)
-            return launch_mode_k<O, A, K, MODE, true>(d, a, stream);
+        if (d->T * d->N / a.hp.num_mini_batch == 2 * 4 * TS && Sm::SBk >= 4 * TS) {
+            if (hp_task) return launch_mode_k<O, A, K, MODE, true, true>(d, with_task_table(a, hp_task), stream);
+            return launch_mode_k<O, A, K, MODE, true, false>(d, a, stream);
+        }
     }
-    return launch_mode_k<O, A, K, MODE, false>(d, a, stream);
+    if (hp_task) return launch_mode_k<O, A, K, MODE, false, true>(d, with_task_table(a, hp_task), stream);
+    return launch_mode_k<O, A, K, MODE, false, false>(d, a, stream);
 }
 
 int fs_choose_ns(const pgm_dims* d, int mb, bool dual_ok, int* dual);
-int ppo_update_fs(const pgm_dims* d, const MArgs& a, int ns, bool dual, hipStream_t stream);
+int ppo_update_fs(const pgm_dims* d, const MArgs& a, int ns, bool dual, hipStream_t stream,
+                  const pgm_task_hparams* hp_task);
 
 // Which obs_dim <= 32 update runs (one rule for the launcher and pgm_ppo_update_variant):
 //   * feature-split with the reduce-scattered Adam (pgm_ppo_fs.hip) while it gets >= FS_AUTO_NS parts per tower
@@ -1805,7 +1816,7 @@ int describe_update_mfma(const pgm_dims* d, const pgm_ppo_hparams* hp, const pgm
 
 template <int O, int A, int K>
 int launch_ppo_update_mfma(const pgm_dims* d, const MArgs& a, const pgm_rollout_buf* rb, const pgm_launch_opts& o,
-                           hipStream_t stream) {
+                           hipStream_t stream, const pgm_task_hparams* hp_task) {
     // packed sample table, then the update
     constexpr int RS = row_stride<O, A, K>();
     static_assert(img_floats<O, A, K>() == ppo_img_floats(O, A, K), "host exchange-slot size out of sync");
@@ -1819,16 +1830,17 @@ int launch_ppo_update_mfma(const pgm_dims* d, const MArgs& a, const pgm_rollout_
     // per lane), so the grid must fit the CU count (choose_update)
     static_assert(sizeof(MSmem<O, A, K, true>) > 80 * 1024, "split residency argument needs > 80 KiB LDS");
     const UpdateChoice c = choose_update(d, d->T * d->N / a.hp.num_mini_batch, o);
-    if (c.kind == 2) return ppo_update_fs(d, a, c.ns, c.dual != 0, stream);
-    if (c.kind == 1) return launch_t16<O, A, K, 4, 4>(d, a, stream);
-    if (c.mode == 2) return launch_mode<O, A, K, 2>(d, a, stream);
-    if (c.mode == 1) return launch_mode<O, A, K, 1>(d, a, stream);
-    return launch_mode<O, A, K, 0>(d, a, stream);
+    if (c.kind == 2) return ppo_update_fs(d, a, c.ns, c.dual != 0, stream, hp_task);
+    if (c.kind == 1) return launch_t16<O, A, K, 4, 4>(d, a, stream, hp_task);
+    if (c.mode == 2) return launch_mode<O, A, K, 2>(d, a, stream, hp_task);
+    if (c.mode == 1) return launch_mode<O, A, K, 1>(d, a, stream, hp_task);
+    return launch_mode<O, A, K, 0>(d, a, stream, hp_task);
 }
 
 int ppo_update_mfma(const pgm_dims* d, const pgm_ppo_hparams* hp, float* params, float* adam_m, float* adam_v,
                     int32_t* adam_step, const float* lr, const int32_t* perms, const pgm_rollout_buf* rb, float* stats,
-                    void* workspace, const pgm_launch_opts& opts, hipStream_t stream) {
+                    void* workspace, const pgm_launch_opts& opts, hipStream_t stream,
+                    const pgm_task_hparams* hp_task) {
     if (!workspace) {
         set_error("pgm_ppo_update: the MFMA update needs the workspace (pgm_ppo_update_workspace_bytes)");
         return PGM_E_INVALID_ARG;
@@ -1845,7 +1857,7 @@ int ppo_update_mfma(const pgm_dims* d, const pgm_ppo_hparams* hp, float* params,
             set_error("pgm_ppo_update: obs_dim %d > 32 not supported by the MFMA update kernel", O);
             return PGM_E_UNSUPPORTED;
         } else {
-            return launch_ppo_update_mfma<O, A, K>(d, a, rb, opts, stream);
+            return launch_ppo_update_mfma<O, A, K>(d, a, rb, opts, stream, hp_task);
         }
     });
 }

@@ -115,14 +115,15 @@ __device__ __forceinline__ float* lds_slot(UpdSmem<O, A, K>& S, const Layout& L,
     return nullptr;
 }
 
-template <int O, int A, int K>
-__global__ __launch_bounds__(UT) void ppo_update_kernel(UpdArgs a) {
+template <int O, int A, int K, bool TASKS>
+__global__ __launch_bounds__(UT) void ppo_update_kernel(TaskArgsT<UpdArgs, TASKS> a) {
     extern __shared__ __attribute__((aligned(16))) char smem_raw[];
     auto& S = *reinterpret_cast<UpdSmem<O, A, K>*>(smem_raw);
     constexpr int OP = upad<O>();
     constexpr int NW1 = (O + 3) / 4;
     constexpr int HQ = hq<A, K>();
     const int p = blockIdx.x, t = threadIdx.x, c = t & (H2 - 1), g = t >> 7, m = c >> 6, j = c & (H - 1);
+    if constexpr (TASKS) take_task_hparams(a.hp, a.hp_task, p);
     const int N = a.N, T = a.T, B = T * N;
     const int E = a.hp.ppo_epoch, M = a.hp.num_mini_batch;
     const int mb = B / M, nb = B / mb;
@@ -495,10 +496,12 @@ __global__ __launch_bounds__(UT) void ppo_update_kernel(UpdArgs a) {
 namespace pgm {
 int ppo_update_mfma(const pgm_dims* d, const pgm_ppo_hparams* hp, float* params, float* adam_m, float* adam_v,
                     int32_t* adam_step, const float* lr, const int32_t* perms, const pgm_rollout_buf* rb, float* stats,
-                    void* workspace, const pgm_launch_opts& o, hipStream_t stream);
+                    void* workspace, const pgm_launch_opts& o, hipStream_t stream,
+                    const pgm_task_hparams* hp_task);
 int ppo_update_wide(const pgm_dims* d, const pgm_ppo_hparams* hp, float* params, float* adam_m, float* adam_v,
                     int32_t* adam_step, const float* lr, const int32_t* perms, const pgm_rollout_buf* rb, float* stats,
-                    void* workspace, const pgm_launch_opts& o, hipStream_t stream);
+                    void* workspace, const pgm_launch_opts& o, hipStream_t stream,
+                    const pgm_task_hparams* hp_task);
 }
 
 using namespace pgm;
@@ -517,7 +520,7 @@ int describe_update_wide(const pgm_dims* d, const pgm_launch_opts& o, char* buf,
 int describe_update_ln(char* buf, int n);
 int ppo_update_ln(const pgm_dims* d, const pgm_ppo_hparams* hp, float* params, float* adam_m, float* adam_v,
                   int32_t* adam_step, const float* lr, const int32_t* perms, const pgm_rollout_buf* rb, float* stats,
-                  void* workspace, hipStream_t stream);
+                  void* workspace, hipStream_t stream, const pgm_task_hparams* hp_task);
 }
 extern "C" int pgm_ppo_update_variant(const pgm_dims* d, const pgm_ppo_hparams* hp, const pgm_launch_opts* opts,
                                       char* buf, int n) {
@@ -564,10 +567,13 @@ extern "C" int pgm_ppo_update_reset(const pgm_dims* d, void* workspace, pgm_stre
     return PGM_OK;
 }
 
-extern "C" int pgm_ppo_update(const pgm_dims* d, const pgm_ppo_hparams* hp, float* params, float* adam_m,
-                              float* adam_v, int32_t* adam_step, const float* lr, const int32_t* perms,
-                              const pgm_rollout_buf* rb, float* stats, void* workspace, const pgm_launch_opts* opts,
-                              pgm_stream_t stream) {
+// pgm_ppo_update (tasks = false) and pgm_ppo_update_tasks: one body, so the checks, their order and their strings are
+// the same; the table check comes last and names its own entry point.  hp_task != nullptr launches the TASKS
+// instantiation of the kernel the selection rule picks.
+static int ppo_update_entry(const pgm_dims* d, const pgm_ppo_hparams* hp, const pgm_task_hparams* hp_task, bool tasks,
+                            float* params, float* adam_m, float* adam_v, int32_t* adam_step, const float* lr,
+                            const int32_t* perms, const pgm_rollout_buf* rb, float* stats, void* workspace,
+                            const pgm_launch_opts* opts, pgm_stream_t stream) {
     if (int rc = check_dims(d, "pgm_ppo_update")) return rc;
     if (int rc = check_ln(d, "pgm_ppo_update")) return rc;
     pgm_launch_opts o;
@@ -582,19 +588,23 @@ extern "C" int pgm_ppo_update(const pgm_dims* d, const pgm_ppo_hparams* hp, floa
         set_error("pgm_ppo_update: need T*N (%d) >= num_mini_batch (%d) > 0 and ppo_epoch > 0", B, hp->num_mini_batch);
         return PGM_E_SHAPE;
     }
+    if (tasks && !hp_task) {
+        set_error("pgm_ppo_update_tasks: null hp_task");
+        return PGM_E_INVALID_ARG;
+    }
     if (d->LN)  // LayerNorm towers: one kernel family, opts ignored
         return ppo_update_ln(d, hp, params, adam_m, adam_v, adam_step, lr, perms, rb, stats, workspace,
-                             (hipStream_t)stream);
+                             (hipStream_t)stream, hp_task);
     // f32-MFMA kernels: obs_dim <= 32 (Walker, Cheetah, Hopper, Ant, Swimmer) with LDS-resident towers, wider
     // observations (Humanoid) with layer 1 in L2; the VALU kernel is kept for A/B measurements
     // (opts.update_kernel = PGM_UPDATE_VALU) and covers obs_dim <= 64
     const bool valu = o.update_kernel == PGM_UPDATE_VALU;
     if (!valu && d->O <= 32)
         return ppo_update_mfma(d, hp, params, adam_m, adam_v, adam_step, lr, perms, rb, stats, workspace, o,
-                               (hipStream_t)stream);
+                               (hipStream_t)stream, hp_task);
     if (!valu && d->O > 64)
         return ppo_update_wide(d, hp, params, adam_m, adam_v, adam_step, lr, perms, rb, stats, workspace, o,
-                               (hipStream_t)stream);
+                               (hipStream_t)stream, hp_task);
     if (d->O > 64) {
         set_error("pgm_ppo_update: obs_dim %d > 64 not supported by the update kernels", d->O);
         return PGM_E_UNSUPPORTED;
@@ -615,16 +625,36 @@ extern "C" int pgm_ppo_update(const pgm_dims* d, const pgm_ppo_hparams* hp, floa
                 set_error("pgm_ppo_update: LDS image %zu bytes exceeds 160 KiB", smem);
                 return PGM_E_UNSUPPORTED;
             }
-            auto kern = ppo_update_kernel<O, A, K>;
-            hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-            if (e != hipSuccess) return hip_fail(e, "pgm_ppo_update");
-            if (workspace && !ws_take_zeroed(workspace, ppo_flag_bytes(d->P))) {
-                // no exchange in this kernel: the timeout word (2P) reads 0 for this call
-                e = hipMemsetAsync(workspace, 0, ppo_flag_bytes(d->P), (hipStream_t)stream);
-                if (e != hipSuccess) return hip_fail(e, "pgm_ppo_update (workspace reset)");
-            }
-            hipLaunchKernelGGL(kern, dim3(d->P), dim3(UT), smem, (hipStream_t)stream, a);
-            return launch_status("pgm_ppo_update");
+            auto launch = [&](auto kern, const auto& ka) -> int {
+                hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                                   (int)smem);
+                if (e != hipSuccess) return hip_fail(e, "pgm_ppo_update");
+                if (workspace && !ws_take_zeroed(workspace, ppo_flag_bytes(d->P))) {
+                    // no exchange in this kernel: the timeout word (2P) reads 0 for this call
+                    e = hipMemsetAsync(workspace, 0, ppo_flag_bytes(d->P), (hipStream_t)stream);
+                    if (e != hipSuccess) return hip_fail(e, "pgm_ppo_update (workspace reset)");
+                }
+                hipLaunchKernelGGL(kern, dim3(d->P), dim3(UT), smem, (hipStream_t)stream, ka);
+                return launch_status("pgm_ppo_update");
+            };
+            if (hp_task) return launch(ppo_update_kernel<O, A, K, true>, with_task_table(a, hp_task));
+            return launch(ppo_update_kernel<O, A, K, false>, a);
         }
     });
+}
+
+extern "C" int pgm_ppo_update(const pgm_dims* d, const pgm_ppo_hparams* hp, float* params, float* adam_m,
+                              float* adam_v, int32_t* adam_step, const float* lr, const int32_t* perms,
+                              const pgm_rollout_buf* rb, float* stats, void* workspace, const pgm_launch_opts* opts,
+                              pgm_stream_t stream) {
+    return ppo_update_entry(d, hp, nullptr, false, params, adam_m, adam_v, adam_step, lr, perms, rb, stats, workspace,
+                            opts, stream);
+}
+
+extern "C" int pgm_ppo_update_tasks(const pgm_dims* d, const pgm_ppo_hparams* hp, const pgm_task_hparams* hp_task,
+                                    float* params, float* adam_m, float* adam_v, int32_t* adam_step, const float* lr,
+                                    const int32_t* perms, const pgm_rollout_buf* rb, float* stats, void* workspace,
+                                    const pgm_launch_opts* opts, pgm_stream_t stream) {
+    return ppo_update_entry(d, hp, hp_task, true, params, adam_m, adam_v, adam_step, lr, perms, rb, stats, workspace,
+                            opts, stream);
 }

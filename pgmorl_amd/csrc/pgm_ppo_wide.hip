@@ -148,8 +148,8 @@ namespace {
 
 // ONE: mb = NS * 4 * 32 (each wave owns exactly one 32-row tile of one pass per minibatch; Humanoid N = 8, NS = 4):
 // the pass loop is straight-line, so the gradient accumulators are not loop-carried
-template <int O, int A, int K, int NS, bool ONE>
-__global__ __launch_bounds__(MT) void ppo_update_wide_kernel(WArgs a) {
+template <int O, int A, int K, int NS, bool ONE, bool TASKS>
+__global__ __launch_bounds__(MT) void ppo_update_wide_kernel(TaskArgsT<WArgs, TASKS> a) {
     static_assert(O > 32 && O % 8 == 0, "wide kernel: obs_dim > 32, multiple of 8 (float4 halves)");
     extern __shared__ __attribute__((aligned(16))) char smem_raw[];
     using Sm = WSmem<A, K>;
@@ -175,6 +175,7 @@ __global__ __launch_bounds__(MT) void ppo_update_wide_kernel(WArgs a) {
     const int p = NS > 1 ? 4 * (bx / (8 * NS)) + (x8 >> 1) : (bx >> 1);
     const int hs = NS == 4 ? 2 * (x8 & 1) + (j8 >> 1) : NS == 2 ? (x8 & 1) : 0;
     if (p >= a.P) return;
+    if constexpr (TASKS) take_task_hparams(a.hp, a.hp_task, p);
     const int m = NS > 1 ? (j8 & 1) : (bx & 1);
     const int NQ = m == 0 ? K : A;
     const int N = a.N, T = a.T, B = T * N;
@@ -1037,7 +1038,8 @@ int describe_update_wide(const pgm_dims* d, const pgm_launch_opts& o, char* buf,
 
 int ppo_update_wide(const pgm_dims* d, const pgm_ppo_hparams* hp, float* params, float* adam_m, float* adam_v,
                     int32_t* adam_step, const float* lr, const int32_t* perms, const pgm_rollout_buf* rb, float* stats,
-                    void* workspace, const pgm_launch_opts& o, hipStream_t stream) {
+                    void* workspace, const pgm_launch_opts& o, hipStream_t stream,
+                    const pgm_task_hparams* hp_task) {
     if (!workspace) {
         set_error("pgm_ppo_update: the wide update needs the workspace (pgm_ppo_update_workspace_bytes)");
         return PGM_E_INVALID_ARG;
@@ -1088,19 +1090,27 @@ int ppo_update_wide(const pgm_dims* d, const pgm_ppo_hparams* hp, float* params,
                 set_error("pgm_ppo_update: LDS image %zu bytes exceeds 160 KiB", smem);
                 return PGM_E_UNSUPPORTED;
             }
-            auto launch = [&](auto kern, int grid) -> int {
+            auto launch_k = [&](auto kern, const auto& ka, int grid) -> int {
                 hipError_t e2 = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize,
                                                     (int)smem);
                 if (e2 != hipSuccess) return hip_fail(e2, "pgm_ppo_update");
                 if (int rc = check_coresident((const void*)kern, MT, smem, grid, "pgm_ppo_update")) return rc;
-                hipLaunchKernelGGL(kern, dim3(grid), dim3(MT), smem, stream, a);
+                hipLaunchKernelGGL(kern, dim3(grid), dim3(MT), smem, stream, ka);
                 return launch_status("pgm_ppo_update");
             };
+            // (NS, ONE) as constants; hp_task picks the TASKS twin of the same kernel
+            auto launch = [&](auto nsc, auto onec, int grid) -> int {
+                constexpr int NS = decltype(nsc)::value;
+                constexpr bool ONE = decltype(onec)::value != 0;
+                if (hp_task)
+                    return launch_k(ppo_update_wide_kernel<O, A, K, NS, ONE, true>, with_task_table(a, hp_task), grid);
+                return launch_k(ppo_update_wide_kernel<O, A, K, NS, ONE, false>, a, grid);
+            };
             const int mb = d->T * d->N / hp->num_mini_batch;
-            if (ns == 4 && mb == 4 * 4 * TS) return launch(ppo_update_wide_kernel<O, A, K, 4, true>, wide_grid(d->P, 4));
-            if (ns == 4) return launch(ppo_update_wide_kernel<O, A, K, 4, false>, wide_grid(d->P, 4));
-            if (ns == 2) return launch(ppo_update_wide_kernel<O, A, K, 2, false>, wide_grid(d->P, 2));
-            return launch(ppo_update_wide_kernel<O, A, K, 1, false>, 2 * d->P);
+            if (ns == 4 && mb == 4 * 4 * TS) return launch(ic<4>{}, ic<1>{}, wide_grid(d->P, 4));
+            if (ns == 4) return launch(ic<4>{}, ic<0>{}, wide_grid(d->P, 4));
+            if (ns == 2) return launch(ic<2>{}, ic<0>{}, wide_grid(d->P, 2));
+            return launch(ic<1>{}, ic<0>{}, 2 * d->P);
         }
     });
 }

@@ -47,10 +47,19 @@ def linear_lr(j, total_num_updates, lr, ratio=1.0):
     return lr - lr * (j * ratio / float(total_num_updates))
 
 
+# the settings a run of a sweep may own (morl.GRID_FIELDS): the learning rate and its decay ratio feed the per-task lr,
+# the others the per-task tables of TaskBatch.set_task_hparams
+RUN_LR_FIELDS = ('lr', 'lr_decay_ratio')
+RUN_TASK_FIELDS = ('gae_lambda', 'clip_param', 'value_loss_coef', 'entropy_coef', 'max_grad_norm')
+
+
 class MOPGPopulation:
     def __init__(self, args, device='cuda', rng='device', host_env=None, device_env=None, env_plugin=None,
-                 run_seeds=None):
-        """run_seeds: the seeds of the runs of a sweep that share this runtime's population (TaskBatch(run_seeds=...));
+                 run_seeds=None, run_hparams=None):
+        """run_hparams (with run_seeds): one dict per run with the settings that run owns (any of RUN_LR_FIELDS and
+        RUN_TASK_FIELDS; a missing key is ``args``' value).  Each generation they are expanded through run_of_task
+        into the per-task tables (TaskBatch.set_task_hparams) and the per-task lr of every iteration.
+        run_seeds: the seeds of the runs of a sweep that share this runtime's population (TaskBatch(run_seeds=...));
         run() and evaluate_samples() then take the run index of every task.  One rank only.
         host_env (default ``args.host_env``, the --host-env flag; None = the device envs): 'synth',
         'module:callable' or a factory (env_name, P, N, seed) -> hostenv.HostVecEnv.  The environments then run on
@@ -90,6 +99,23 @@ class MOPGPopulation:
             from ._lib import PGMError
             raise PGMError(f'run_seeds=... on {world()[1]} ranks: a multi-run population lives on one GPU '
                            f'(multi-GPU sweeps are not built)')
+        self.run_hparams = None
+        if run_hparams is not None:
+            from ._lib import PGMError
+            from .runtime import check_task_hparam
+            if self.run_seeds is None or len(run_hparams) != len(self.run_seeds):
+                raise PGMError(f'run_hparams=... holds one dict per run of run_seeds=...: got '
+                               f'{len(run_hparams)} for {0 if self.run_seeds is None else len(self.run_seeds)} runs')
+            self.run_hparams = [dict(h) for h in run_hparams]
+            for h in self.run_hparams:
+                for k, v in h.items():
+                    if k in RUN_TASK_FIELDS:
+                        check_task_hparam(k, v, 'run_hparams')
+                    elif k not in RUN_LR_FIELDS:
+                        raise PGMError(f'run_hparams: {k!r} is not a per-run setting (one of '
+                                       f'{", ".join(RUN_LR_FIELDS + RUN_TASK_FIELDS)})')
+                    elif not np.isfinite(float(v)):
+                        raise PGMError(f'run_hparams: {k}={v!r} must be finite')
 
     @property
     def layout(self):
@@ -272,6 +298,23 @@ class MOPGPopulation:
             raise PGMError(f'run_of_task has {len(run_of_task)} ids for {n} tasks')
         tb.set_runs(run_of_task)
 
+    def run_lr(self, r, j, total):
+        """Run r's learning rate of iteration j: the host expression of a solo run with that run's lr and
+        lr_decay_ratio, in Python floats (the fp32 rounding happens once, at the upload)."""
+        a, h = self.args, self.run_hparams[r]
+        lr0, ratio = float(h.get('lr', a.lr)), float(h.get('lr_decay_ratio', a.lr_decay_ratio))
+        return linear_lr(j, total, lr0, ratio) if a.use_linear_lr_decay else lr0
+
+    def task_lr(self, run_of_task, j, total):
+        """[P] fp32: every task's learning rate of iteration j (run_lr of its run, rounded to fp32)."""
+        per_run = [self.run_lr(r, j, total) for r in range(len(self.run_hparams))]
+        return np.asarray([per_run[r] for r in run_of_task], dtype=np.float64).astype(np.float32)
+
+    def task_hparams(self, run_of_task):
+        """{field: [P] list} of RUN_TASK_FIELDS: every task's settings, its run's dict over ``args``."""
+        a = self.args
+        return {k: [float(self.run_hparams[r].get(k, getattr(a, k))) for r in run_of_task] for k in RUN_TASK_FIELDS}
+
     def run(self, task_batch, iteration, num_updates, start_time=None, log=print, run_of_task=None):
         """Every task's MOPG iterations [iteration, iteration + num_updates) -> all_offspring_batch.
         run_of_task (with run_seeds): the run index of every task, whose reset tables it uses.
@@ -305,6 +348,8 @@ class MOPGPopulation:
                             [t.scalarization.weights.numpy() for t in task_batch[lo:hi]])
             step0 = [t.sample.snapshot.adam_step for t in task_batch[lo:hi]]
             self._set_runs(tb, run_of_task, Pl)
+            if self.run_hparams is not None:
+                tb.set_task_hparams(**self.task_hparams(run_of_task))
             tb.env_reset()  # envs are re-created and reset every generation (mopg.py:67-82)
             arena = torch.empty(I, 3, Pl, L, dtype=torch.float32, device=self.device)
             store = RowStore(arena, 'arena')
@@ -312,6 +357,8 @@ class MOPGPopulation:
             objs_ar = torch.empty(I, Pl, tb.K, dtype=torch.float64, device=self.device)  # written by the evals
             for i, j in enumerate(its):
                 lr = linear_lr(j, total, a.lr, a.lr_decay_ratio) if a.use_linear_lr_decay else a.lr
+                if self.run_hparams is not None:
+                    lr = self.task_lr(run_of_task, j, total)
                 noise = perms = None
                 if self.rng == 'host' and tb.discrete:
                     noise, perms = host_draws_discrete(j, a.num_steps, a.num_processes, a.ppo_epoch)

@@ -256,6 +256,10 @@ def run(args, device='cuda', rng='device', log=print, runtime=None, host_env=Non
 
 # ---------------------------------------------------------------------------------------------- several runs at once
 SWEEP_FIELDS = ('seed', 'selection_method', 'save_dir')  # what the runs of one run_many may differ in
+# what they may differ in besides, when run_many(vary=...) names it: the settings that are per task on the device (lr is
+# [P]; the others are TaskBatch.set_task_hparams' tables).  Not gamma (it also enters the rollout's return normalisation
+# and the evaluation discount) and not the shapes.
+GRID_FIELDS = ('lr', 'lr_decay_ratio', 'gae_lambda', 'clip_param', 'value_loss_coef', 'entropy_coef', 'max_grad_norm')
 
 
 class _HostStreams:
@@ -270,16 +274,21 @@ class _HostStreams:
         torch.set_rng_state(self.torch_state)
 
 
-def check_sweep_args(args_list):
+def check_sweep_args(args_list, vary=()):
     """The runs of a sweep share one population, so they may differ in SWEEP_FIELDS only; ValueError naming the first
-    other field that differs."""
+    other field that differs.  vary: names out of GRID_FIELDS that may differ as well (any other name: ValueError)."""
+    vary = tuple(vary)
+    for k in vary:
+        if k not in GRID_FIELDS:
+            raise ValueError(f'run_many: vary={k!r} is not a per-task setting; the runs of a sweep may vary in '
+                             f'{", ".join(GRID_FIELDS)} only')
     if not args_list:
         raise ValueError('run_many: no runs')
     first = vars(args_list[0])
     for i, a in enumerate(args_list[1:], 1):
         va = vars(a)
         for k in sorted(set(first) | set(va)):
-            if k in SWEEP_FIELDS:
+            if k in SWEEP_FIELDS or k in vary:
                 continue
             if k not in first or k not in va or first[k] != va[k]:
                 raise ValueError(f'run_many: run {i} differs from run 0 in {k!r} ({va.get(k)!r} != {first.get(k)!r}); '
@@ -312,7 +321,7 @@ def sweep_chunks(args_list, max_tasks=None, fits=None):
     return [list(range(i, min(i + cap, n))) for i in range(0, n, cap)]
 
 
-def run_many(args_list, device='cuda', rng='device', log=None, runtime=None, max_tasks=None, info=None):
+def run_many(args_list, device='cuda', rng='device', log=None, runtime=None, max_tasks=None, info=None, vary=()):
     """Several runs of the generation loop (one args object each, differing in seed, selection_method and save_dir
     only) on ONE device population: per generation the runs' task batches are concatenated in run order, the runtime
     is called once with the run index of every task (MOPGPopulation(run_seeds=...): a task resets from its own run's
@@ -328,9 +337,13 @@ def run_many(args_list, device='cuda', rng='device', log=None, runtime=None, max
     MOPGPopulation declares ('torch',) with rng='host'.  A runtime that merely draws from a global stream has no place
     here: its draws would depend on which run's state happened to be installed.
     max_tasks: most tasks of one launch; more runs are processed in consecutive chunks (sweep_chunks).
+    vary: fields out of GRID_FIELDS in which the runs may differ as well (a hyper-parameter grid).  The runtime factory
+    is then called as (args, run_seeds, run_hparams=[{field: value} per run of the chunk]); MOPGPopulation expands the
+    dicts through run_of_task into per-task device tables and the per-task lr.  With the default () nothing changes.
     info: a dict that receives the chunking, the tasks per generation and the wall / MOPG / boundary seconds."""
     args_list = list(args_list)
-    check_sweep_args(args_list)
+    vary = tuple(vary)
+    check_sweep_args(args_list, vary)
     if world()[1] > 1:
         raise ValueError('run_many: a sweep runs on one rank (multi-GPU sweeps are not built)')
     if log is None or isinstance(log, (list, tuple)):
@@ -341,8 +354,8 @@ def run_many(args_list, device='cuda', rng='device', log=None, runtime=None, max
         raise ValueError(f'run_many: {len(logs)} logs for {len(args_list)} runs')
     make = runtime
     if make is None:
-        def make(a, run_seeds):
-            return MOPGPopulation(a, device=device, rng=rng, run_seeds=run_seeds)
+        def make(a, run_seeds, run_hparams=None):
+            return MOPGPopulation(a, device=device, rng=rng, run_seeds=run_seeds, run_hparams=run_hparams)
     fits = None
     if runtime is None:
         fits = lambda P: MOPGPopulation.update_fits(args_list[0], P, device)  # noqa: E731
@@ -352,7 +365,8 @@ def run_many(args_list, device='cuda', rng='device', log=None, runtime=None, max
            'boundary_s': [0.0] * len(args_list), 'generations': []}
     eps = [None] * len(args_list)
     for chunk in chunks:
-        for i, ep in zip(chunk, _run_chunk([args_list[i] for i in chunk], [logs[i] for i in chunk], make, rec, chunk)):
+        for i, ep in zip(chunk, _run_chunk([args_list[i] for i in chunk], [logs[i] for i in chunk], make, rec, chunk,
+                                           vary)):
             eps[i] = ep
     rec['wall_s'] = time.perf_counter() - t_wall
     if info is not None:
@@ -360,7 +374,7 @@ def run_many(args_list, device='cuda', rng='device', log=None, runtime=None, max
     return eps
 
 
-def _run_chunk(args_list, logs, make, rec, ids):
+def _run_chunk(args_list, logs, make, rec, ids, vary=()):
     """One complete multi-run over args_list (run_many)."""
     R = len(args_list)
     runs, streams = [], [_HostStreams() for _ in range(R)]
@@ -368,7 +382,11 @@ def _run_chunk(args_list, logs, make, rec, ids):
     for a, lg, hs in zip(args_list, logs, streams):
         runs.append(_Run(a, lg))  # seeds the global streams with the run's seed
         if rt is None:
-            rt = make(args_list[0], [x.seed for x in args_list])
+            if vary:
+                rt = make(args_list[0], [x.seed for x in args_list],
+                          run_hparams=[{k: getattr(x, k) for k in vary} for x in args_list])
+            else:
+                rt = make(args_list[0], [x.seed for x in args_list])
         runs[-1].setup()
         hs.save()
     # warm-up: every run's policies drawn from its own streams, then ONE evaluation of all of them

@@ -35,13 +35,35 @@ import torch
 from . import envspec
 from ._lib import (ANY_MAX_ACT, ANY_MAX_OBJ, ANY_MAX_OBS, Dims, DstSpec, DummySpec, EnvSpec, EnvState, NormState,
                    PGMError, PPOHParams, RolloutBuf, check, launch_opts, lib, require_any_dims, require_categorical,
-                   require_dst_device, require_dummy_device, require_runs)
+                   require_dst_device, require_dummy_device, require_runs, require_tasks, TASK_HPARAM_FIELDS)
 from .layout import ParamLayout
 
 F32, F64, I32 = torch.float32, torch.float64, torch.int32
 LN_MAX_OBS = 32  # layernorm=True: the five envs with obs_dim <= 32 (include/pgm_abi.h pgm_dims.LN)
 UPDATE_TIMEOUT_MSG = ('pgm_ppo_update: a cross-workgroup exchange timed out (workspace word 2P set); the update '
                       'kernel\'s workgroups were not co-resident -- the parameters are invalid')
+
+
+# the per-task settings of set_task_hparams: pgm_task_hparams' fields in order, then the GAE lambda
+TASK_FIELDS = TASK_HPARAM_FIELDS + ('gae_lambda',)
+
+
+def check_task_hparam(name, values, what='set_task_hparams'):
+    """The host checks of one per-task setting (the kernels trust the device tables): finite, clip_param > 0,
+    max_grad_norm > 0, 0 <= gae_lambda <= 1.  Returns the values as a float64 array; PGMError naming the field."""
+    if name not in TASK_FIELDS:
+        raise PGMError(f'{what}: {name!r} is not a per-task setting (one of {", ".join(TASK_FIELDS)})')
+    try:
+        v = np.asarray(values, dtype=np.float64)
+    except (TypeError, ValueError):
+        raise PGMError(f'{what}: {name}={values!r} is not a number or an array of numbers') from None
+    if not np.all(np.isfinite(v)):
+        raise PGMError(f'{what}: {name}={np.ravel(v).tolist()} must be finite')
+    if name in ('clip_param', 'max_grad_norm') and not np.all(v > 0):
+        raise PGMError(f'{what}: {name}={np.ravel(v).tolist()} must be > 0')
+    if name == 'gae_lambda' and not np.all((v >= 0) & (v <= 1)):
+        raise PGMError(f'{what}: {name}={np.ravel(v).tolist()} must be in [0, 1]')
+    return v
 
 
 def _ptr(t):
@@ -288,6 +310,7 @@ class TaskBatch:
                              max_grad_norm=max_grad_norm, adam_eps=adam_eps, beta1=0.9, beta2=0.999,
                              ppo_epoch=ppo_epoch, num_mini_batch=num_mini_batch,
                              use_clipped_value_loss=int(use_clipped_value_loss))
+        self.hp_task, self.lam_task = None, None  # device tables of set_task_hparams (None: the shared settings)
         self._eval_stream, self._eval_done = None, None
         self._reset_pending = False  # a pgm_ppo_update_reset queued on the side stream, not yet waited for
         ws_bytes = lib().pgm_ppo_update_cat_workspace_bytes if self.discrete else lib().pgm_ppo_update_workspace_bytes
@@ -501,6 +524,52 @@ class TaskBatch:
             raise PGMError(f'set_runs: run ids must be integers in [0, {len(self.run_seeds)}), got {ids.tolist()}')
         self.run_of_task[:self.P].copy_(torch.from_numpy(ids.astype(np.int32)))
 
+    def set_task_hparams(self, clip_param=None, value_loss_coef=None, entropy_coef=None, max_grad_norm=None,
+                         gae_lambda=None):
+        """Per-task PPO settings (the runs of a hyper-parameter grid in one population): each argument is a scalar or a
+        length-P array over the active tasks; None keeps the batch's shared value.  Checked here (the kernels trust the
+        device tables), then uploaded into ``hp_task`` [capacity][4] / ``lam_task`` [capacity]; from the first call on
+        gae() and ppo_update_launch() go through pgm_gae_tasks / pgm_ppo_update_tasks.  A batch that never calls this
+        launches what it always launched.  Plain and LayerNorm Gaussian batches on the SynthMO device envs only."""
+        for flag, on in (('discrete actions', self.discrete), ('any_dims', self.any_dims),
+                         ('env_plugin', self.plugin is not None), ('device_env', self.device_env),
+                         ('an MO-Dummy env', self.dummy_env), ('host_env', self.host_env is not None)):
+            if on:
+                raise PGMError(f'set_task_hparams: per-task PPO settings exist for the update kernels of '
+                               f'pgm_ppo_update on the SynthMO device envs only; this batch has {flag}')
+        given = dict(clip_param=clip_param, value_loss_coef=value_loss_coef, entropy_coef=entropy_coef,
+                     max_grad_norm=max_grad_norm, gae_lambda=gae_lambda)
+        P = self.P
+        rows = {}
+        for name, val in given.items():
+            if val is None:
+                val = self.gae_lambda if name == 'gae_lambda' else getattr(self.hp, name)
+            v = check_task_hparam(name, val)
+            if v.ndim > 1 or (v.ndim == 1 and len(v) != P):
+                raise PGMError(f'set_task_hparams: {name} has shape {v.shape} for {P} active tasks (a scalar or one '
+                               f'value per task)')
+            rows[name] = np.broadcast_to(v.astype(np.float32), (P,))
+        require_tasks()
+        if self.hp_task is None:  # every slot starts at the shared values
+            shared = [getattr(self.hp, n) for n in TASK_HPARAM_FIELDS]
+            self.hp_task = torch.tensor([shared] * self.capacity, dtype=F32, device=self.dev)
+            self.lam_task = torch.full((self.capacity,), float(self.gae_lambda), dtype=F32, device=self.dev)
+        tab = np.stack([rows[n] for n in TASK_HPARAM_FIELDS], axis=1)
+        self.hp_task[:P].copy_(torch.from_numpy(np.ascontiguousarray(tab)))
+        self.lam_task[:P].copy_(torch.from_numpy(np.array(rows['gae_lambda'])))
+
+    def set_lr(self, lr):
+        """The learning rate of the next update: a scalar for every task, or one value per active task (rounded to
+        fp32 exactly as the scalar is)."""
+        if np.ndim(lr) == 0:
+            self.lr.fill_(float(lr))
+            return
+        v = np.asarray(lr, dtype=np.float64)
+        if v.shape != (self.P,):
+            raise PGMError(f'iteration: lr has shape {v.shape} for {self.P} active tasks (a scalar or one value per '
+                           f'task)')
+        self.lr.copy_(torch.from_numpy(v.astype(np.float32)))
+
     @property
     def state(self):
         """[3][P][L] view of the active slots (params | exp_avg | exp_avg_sq); strided when P < capacity."""
@@ -697,6 +766,10 @@ class TaskBatch:
                                 int(carry), C.byref(launch_opts()), _stream()), 'pgm_rollout')
 
     def gae(self):
+        if self.lam_task is not None:
+            check(lib().pgm_gae_tasks(C.byref(self.dims), C.byref(self.c_rb), self.gamma, _ptr(self.lam_task),
+                                      int(self.use_gae), int(self.proper), _stream()), 'pgm_gae_tasks')
+            return
         check(lib().pgm_gae(C.byref(self.dims), C.byref(self.c_rb), self.gamma, self.gae_lambda, int(self.use_gae),
                             int(self.proper), _stream()), 'pgm_gae')
 
@@ -739,6 +812,13 @@ class TaskBatch:
                                            _ptr(self.adam_v), _ptr(self.adam_step), _ptr(self.lr), _ptr(self.perms),
                                            C.byref(self.c_rb), _ptr(self.stats), _ptr(self.update_ws), _stream()),
                   'pgm_ppo_update_cat')
+            return
+        if self.hp_task is not None:
+            check(lib().pgm_ppo_update_tasks(C.byref(self.dims), C.byref(self.hp), _ptr(self.hp_task),
+                                             _ptr(self.params), _ptr(self.adam_m), _ptr(self.adam_v),
+                                             _ptr(self.adam_step), _ptr(self.lr), _ptr(self.perms), C.byref(self.c_rb),
+                                             _ptr(self.stats), _ptr(self.update_ws), C.byref(launch_opts()),
+                                             _stream()), 'pgm_ppo_update_tasks')
             return
         check(lib().pgm_ppo_update(C.byref(self.dims), C.byref(self.hp), _ptr(self.params), _ptr(self.adam_m),
                                    _ptr(self.adam_v), _ptr(self.adam_step), _ptr(self.lr), _ptr(self.perms),
@@ -824,7 +904,7 @@ class TaskBatch:
         """One MOPG iteration for every task: rollout, returns, advantages, PPO update, evaluation.
 
         noise/perms: the reference's RNG draws of iteration j (parity mode); None draws the
-        device counter streams keyed by j (perf mode).
+        device counter streams keyed by j (perf mode).  lr: a scalar, or one value per active task.
 
         overlap_eval: the evaluation of this iteration's snapshot (mopg.py:146-155) runs on a side stream,
         concurrently with the NEXT iteration's rollout / returns / advantages (which only read the
@@ -847,12 +927,12 @@ class TaskBatch:
             side = self.eval_stream  # (behind the previous evaluation, itself behind the previous update)
             side.wait_stream(torch.cuda.current_stream())
             with torch.cuda.stream(side):
-                self.lr.fill_(float(lr))
+                self.set_lr(lr)
                 self.make_perms(j)
                 perm_ready = torch.cuda.Event()
                 perm_ready.record(side)
         else:
-            self.lr.fill_(float(lr))
+            self.set_lr(lr)
         self.rollout(j, noise=noise, carry=carry)
         self.gae()
         self.adv_normalize()

@@ -2,15 +2,24 @@
 selected method, every run --num-tasks tasks), with all runs sharing ONE device population (morl.run_many):
 
     python -m pgmorl_amd.sweep [--pgmorl] [--ra] [--pfa] [--moead] [--random] [--num-seeds 6] [--seeds S ...] \
-           --save-dir ROOT [--max-tasks M] -- <any pgmorl_amd.run flag except --seed / --selection-method / --save-dir>
+           [--grid FLAG V1 [V2 ...]]... --save-dir ROOT [--max-tasks M] \
+           -- <any pgmorl_amd.run flag except --seed / --selection-method / --save-dir>
 
 Run i of method m writes ROOT/<m>/<i>/ (m in pgmorl, ra, pfa, moead, random) with the args.txt, log.txt, generation
 directories, final/ and timing.json of a solo ``python -m pgmorl_amd.run``; ROOT/sweep_timing.json holds the sweep's
 wall time, its MOPG time, the per-run boundary times, the chunking and the tasks per generation.  The default seeds are
 the launcher's own draw: random.seed(1000), one randint(0, 1000000) per seed index, shared by the methods of that index.
+
+--grid FLAG V1 [V2 ...] (repeatable; FLAG one of lr, lr-decay-ratio, gae-lambda, clip-param, value-loss-coef,
+entropy-coef, max-grad-norm) adds a hyper-parameter grid: the runs are the cartesian product of the grids, the seeds
+and the methods, all in the same population (the settings are per task on the device), and a run lands in
+ROOT/<m>/<point>/<i>/ with <point> the grids' flag=value joined by commas in the order given, e.g.
+lr=0.0003,clip-param=0.1.  The runs are ordered grid point outermost, then seed index, then method.
 """
 import argparse
+import itertools
 import json
+import math
 import os
 import random
 import sys
@@ -18,6 +27,11 @@ import sys
 # launcher flag -> (--selection-method, directory), in the launchers' own order inside one seed index
 METHODS = (('pgmorl', 'prediction-guided'), ('ra', 'ra'), ('random', 'random'), ('pfa', 'pfa'), ('moead', 'moead'))
 OWN_FLAGS = ('--seed', '--selection-method', '--save-dir')  # set per run by the sweep
+# --grid flags that are refused with a reason of their own (the others outside morl.GRID_FIELDS are unknown)
+NOT_PER_TASK = {'gamma': 'gamma also enters the rollout\'s return normalisation and the evaluation discount, which are '
+                         'not per task',
+                **{k: f'{k} is a shape of the shared rollout storage and update launch'
+                   for k in ('num-steps', 'num-processes', 'ppo-epoch', 'num-mini-batch')}}
 
 
 def default_seeds(n):
@@ -37,12 +51,66 @@ def get_parser():
     ap.add_argument('--save-dir', required=True, metavar='ROOT')
     ap.add_argument('--max-tasks', type=int, default=None,
                     help='most tasks of one launch; more runs are processed in consecutive chunks')
+    ap.add_argument('--grid', action='append', nargs='+', default=None, metavar=('FLAG', 'V'),
+                    help='a hyper-parameter grid: FLAG V1 [V2 ...]; repeatable, the runs are the cartesian product')
     return ap
+
+
+def _full_flag(given):
+    """The run flag argparse reads `given` as: itself, or the one flag it is an unambiguous prefix of (else None)."""
+    from .run import get_parser as run_parser
+    known = list(run_parser()._option_string_actions)
+    if given in known:
+        return given
+    hits = [k for k in known if k.startswith(given)]
+    return hits[0] if len(hits) == 1 else None
+
+
+def grid_points(grids, rest):
+    """[(field, flag, [value text, ...])] of the --grid options, after every refusal (PGMError naming the flag)."""
+    from ._lib import PGMError
+    from .morl import GRID_FIELDS
+    from .runtime import TASK_FIELDS, check_task_hparam
+    out = []
+    for g in grids or []:
+        flag = g[0].replace('_', '-')
+        field = flag.replace('-', '_')
+        if flag in NOT_PER_TASK:
+            raise PGMError(f'--grid {flag}: {NOT_PER_TASK[flag]}; the runs of one population share it '
+                           f'(grids: {", ".join(k.replace("_", "-") for k in GRID_FIELDS)})')
+        if field not in GRID_FIELDS:
+            raise PGMError(f'--grid {flag}: unknown grid flag (one of '
+                           f'{", ".join(k.replace("_", "-") for k in GRID_FIELDS)})')
+        if any(field == f for f, _, _ in out):
+            raise PGMError(f'--grid {flag} given twice: one value list per flag')
+        for a in rest:
+            given = a.split('=')[0]
+            if given.startswith('--') and len(given) > 2 and _full_flag(given) == f'--{flag}':
+                raise PGMError(f'--grid {flag} and {given} after "--": the grid sets --{flag} of every run itself')
+        texts = list(g[1:])
+        if not texts:
+            raise PGMError(f'--grid {flag}: no values')
+        vals = []
+        for t in texts:
+            try:
+                v = float(t)
+            except ValueError:
+                raise PGMError(f'--grid {flag}: {t!r} is not a number') from None
+            if field in TASK_FIELDS:
+                check_task_hparam(field, v, f'--grid {flag}')
+            elif not math.isfinite(v):
+                raise PGMError(f'--grid {flag}: {t} must be finite')
+            if v in vals:
+                raise PGMError(f'--grid {flag}: the value {t} is listed twice')
+            vals.append(v)
+        out.append((field, flag, vals))
+    return out
 
 
 def plan(argv):
     """(sweep options, run argv, [(method dir, seed index, run argv of that run)]) after every refusal; touches neither
-    the file system nor the device."""
+    the file system nor the device.  With --grid the first element of a triple is <method>/<point>, and opts.vary names
+    the fields the runs differ in (morl.run_many's vary; () without a grid)."""
     from ._lib import PGMError
     from . import envspec
     from .run import get_parser as run_parser, merge_argv
@@ -55,6 +123,8 @@ def plan(argv):
         if own_flag:  # (argparse also takes an unambiguous prefix, --see 3)
             raise PGMError(f'{own_flag[0]} after "--": the sweep sets --seed, --selection-method and --save-dir of '
                            f'every run itself (--seeds, the method flags, --save-dir ROOT)')
+    grids = grid_points(opts.grid, rest)
+    opts.vary = tuple(field for field, _, _ in grids)
     methods = [(flag, m) for flag, m in METHODS if getattr(opts, flag)]
     if not methods:
         raise PGMError('no selection method: pass at least one of --pgmorl --ra --pfa --moead --random')
@@ -90,10 +160,15 @@ def plan(argv):
         if opts.max_tasks < tasks_per_run(base):
             raise PGMError(f'--max-tasks {opts.max_tasks} is below the {tasks_per_run(base)} tasks of one run')
     runs = []
-    for i, seed in enumerate(seeds):
-        for flag, m in methods:
-            d = os.path.join(opts.save_dir, flag, str(i))
-            runs.append((flag, i, rest + ['--seed', str(seed), '--selection-method', m, '--save-dir', d]))
+    for point in itertools.product(*[vals for _, _, vals in grids]):
+        # (no grid: one empty point, the directories and argv of a sweep without --grid)
+        name = ','.join(f'{gflag}={v!r}' for (_, gflag, _), v in zip(grids, point))
+        pargv = [x for (_, gflag, _), v in zip(grids, point) for x in (f'--{gflag}', repr(v))]
+        for i, seed in enumerate(seeds):
+            for flag, m in methods:
+                top = os.path.join(flag, name) if grids else flag
+                d = os.path.join(opts.save_dir, top, str(i))
+                runs.append((top, i, rest + pargv + ['--seed', str(seed), '--selection-method', m, '--save-dir', d]))
     return opts, base, runs
 
 
@@ -120,7 +195,7 @@ def main(argv=None):
     from .mopg import MOPGPopulation
     args_list = [run_parser().parse_args(merge_argv(rargv)) for _, _, rargv in runs]
     # run_many's own refusals, before ROOT is made (it checks again)
-    check_sweep_args(args_list)
+    check_sweep_args(args_list, opts.vary)
     sweep_chunks(args_list, opts.max_tasks, lambda P: MOPGPopulation.update_fits(args_list[0], P, base.device))
     logs = []
     for a, (flag, i, rargv) in zip(args_list, runs):
@@ -130,7 +205,8 @@ def main(argv=None):
         logs.append(_RunLog(os.path.join(a.save_dir, 'log.txt'), f'{flag}/{i}'))
     info = {}
     try:
-        run_many(args_list, device=base.device, rng=base.rng, log=logs, max_tasks=opts.max_tasks, info=info)
+        run_many(args_list, device=base.device, rng=base.rng, log=logs, max_tasks=opts.max_tasks, info=info,
+                 vary=opts.vary)
     finally:
         for lg in logs:
             lg.f.close()

@@ -1,4 +1,4 @@
-"""Compare the -Rpass-analysis=kernel-resource-usage lines of two builds of the same sources (DESIGN.md §25).
+"""Compare the -Rpass-analysis=kernel-resource-usage lines of two builds of the same sources (DESIGN.md §25, §26).
 
     hipcc -O3 -std=c++17 --offload-arch=gfx950 -I include -Rpass-analysis=kernel-resource-usage --cuda-device-only \
         -c pgmorl_amd/csrc/pgm_rollout_lanes.hip -o /dev/null 2> lanes.remarks      (once per tree)
@@ -6,6 +6,10 @@
 
 Each directory holds *.remarks files.  Kernels are matched by demangled name with the template arguments this change
 adds (the trailing RUNS flag and the argument-block type) removed; the RUNS = true instantiations are listed apart.
+§25: pgm_policy_env.hip, pgm_rollout_lanes.hip, pgm_rollout_wide.hip.  §26 (the trailing flag is TASKS):
+pgm_ppo_fs.hip, pgm_ppo_mfma.hip, pgm_ppo_wide.hip, pgm_ppo_update.hip, pgm_ppo_ln.hip, pgm_misc.hip, and
+pgm_ppo_cat.hip and pgm_ppo_any.hip, which share headers with them and gain no flag.  The parent's names are taken as they are (a parent
+kernel whose own last template argument is a bool keeps it).
 """
 import glob
 import json
@@ -34,23 +38,33 @@ def parse(d):
     return {d_: out[n] for n, d_ in zip(names, dem)}
 
 
-def key(name):
-    """(kernel<args> without the RUNS flag, RUNS)"""
+def key(name, strip=True):
+    """(kernel<args> without the trailing RUNS / TASKS flag, the flag); strip=False: the name as it is, False"""
     name = name.replace('(anonymous namespace)::', '').replace('void ', '')  # (before the cut at the argument list)
     name = re.sub(r'\(.*$', '', name)
-    m = re.match(r'(.*), (true|false)>$', name)
+    m = re.match(r'(.*), (true|false)>$', name) if strip else None
     if m:
         return m.group(1) + '>', m.group(2) == 'true'
+    m = re.match(r'(.*)<(true|false)>$', name) if strip else None  # (a kernel whose one template argument is the flag)
+    if m:
+        return m.group(1), m.group(2) == 'true'
     return name, False
+
+
+def head_key(name, base_names):
+    """key() of a branch kernel; a name the parent has as it stands is that kernel (its last bool is its own)"""
+    plain = key(name, strip=False)
+    return plain if plain[0] in base_names else key(name)
 
 
 def main():
     base, head = parse(sys.argv[1]), parse(sys.argv[2])
+    base_names = {key(n, strip=False)[0] for n in base}
     def keyed(fns, full):
         """{key: lines}; two functions under one key would hide each other: refused"""
         out = {}
         for n, v in fns.items():
-            k = key(n) if full else key(n)[0]
+            k = head_key(n, base_names) if full else key(n, strip=False)[0]
             if k in out:
                 sys.exit(f'two kernels share the key {k!r} (last: {n})')
             out[k] = v

@@ -608,6 +608,26 @@ int pgm_ppo_update_any(const pgm_dims* d, int32_t head, const pgm_ppo_hparams* h
                        const pgm_rollout_buf* rb, float* stats, void* workspace, pgm_stream_t stream);
 size_t pgm_ppo_update_any_workspace_bytes(const pgm_dims* d); /* monotone in d->P */
 
+/* ---- Re-evaluation of a saved Pareto set (discovered by the presence of the symbol pgm_eval_episodes; no feature bit,
+ * no version change).  evaluation() (morl/mopg.py:25-46) of each of d->P = M policies (d->N and d->T are not read) from
+ * each of the E start states starts [E][O], on the SynthMO device envs; M is not a training population and may be in
+ * the thousands.  Grid (M, ceil(E / 8)), 256 threads: workgroup (m, c) runs episodes 8c .. min(8c + 8, E) - 1 of
+ * policy m as the rows of one policy forward per step, with the arithmetic of pgm_eval's block kernel row by row.
+ * ob_mean / ob_var [M][O]: each policy's own frozen statistics (use_ob_rms).  stochastic != 0: the action is
+ * fmaf(z, exp(logstd), mean) before the env's clip, z for (episode e, step t, action dim j) being element
+ * (e * spec->max_episode_steps + t) * A + j of the counter stream pgm_normal_noise(noise_seed) -- the same for every
+ * policy (common random numbers across the front); stochastic == 0 does not read noise_seed.
+ * episodes_out [M][E][K] fp64: each episode's sum of g * obj, g = gamma^t unless raw.  objs_out [M][K] (may be NULL):
+ * the episode sums added in index order, divided by E.
+ * Validation, before any device work, in this order: NULL pointers (d, params, spec, starts, episodes_out; ob_mean /
+ * ob_var with use_ob_rms) PGM_E_INVALID_ARG; the dims with N = 1, T = 0 as pgm_eval_act checks them; pgm_dims.LN;
+ * a NULL field of spec or max_episode_steps <= 0 PGM_E_INVALID_ARG; 1 <= E <= 65536 else PGM_E_SHAPE; then a dim set
+ * no kernel is compiled for PGM_E_UNSUPPORTED. */
+int pgm_eval_episodes(const pgm_dims* d, const float* params, const pgm_env_spec* spec, const double* ob_mean,
+                      const double* ob_var, const double* starts, int32_t E, int32_t use_ob_rms, int32_t raw,
+                      double gamma, int32_t stochastic, uint64_t noise_seed, double* episodes_out, double* objs_out,
+                      pgm_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -13,7 +13,8 @@ LIB = os.path.join(HERE, 'libpgm.so')
 OBJDIR = os.path.join(HERE, 'build')
 SOURCES = ['pgm_abi.cpp', 'pgm_policy_env.hip', 'pgm_rollout_lanes.hip', 'pgm_rollout_wide.hip', 'pgm_misc.hip', 'pgm_ppo_update.hip',
            'pgm_ppo_mfma.hip', 'pgm_ppo_fs.hip', 'pgm_ppo_wide.hip', 'pgm_ppo_ln.hip', 'pgm_hostenv.hip',
-           'pgm_ppo_cat.hip', 'pgm_dst.hip', 'pgm_dummy.hip', 'pgm_anydims.hip', 'pgm_ppo_any.hip']
+           'pgm_ppo_cat.hip', 'pgm_dst.hip', 'pgm_dummy.hip', 'pgm_anydims.hip', 'pgm_ppo_any.hip',
+           'pgm_eval_episodes.hip']
 HEADERS = ['pgm_common.hpp', 'pgm_dispatch.hpp', 'pgm_rollout.hpp', 'pgm_mfma.hpp', 'pgm_ppo_shared.hpp',
            'pgm_policy_dev.hpp', 'pgm_ppo_terms.hpp', 'pgm_ppo_tower.hpp', 'pgm_dst.hpp', 'pgm_dummy.hpp', 'pgm_anydims.hpp']
 ARCH = os.environ.get('PGM_OFFLOAD_ARCH', 'gfx950')

@@ -50,6 +50,30 @@
  * The forced limit: the caller counts the steps of the running episode (`elapsed`).  On the step that brings the count
  * to MAX_STEPS it sets done = 1 and bad = 1, whatever step reported.  That bound makes every loop of the kernels and
  * of the host functions finite; it is not optional.
+ *
+ * ---- contract 2: runtime parameters and per-step uniforms (optional)
+ *
+ * A header that declares `static constexpr int CONTRACT = 2;` asks for two more inputs.  Absent, or 1, is the contract
+ * above and nothing below applies.  With CONTRACT == 2 the header also declares
+ *       static constexpr int NP;             fp64 runtime parameters of the env, 0 <= NP <= 16
+ *       static constexpr int NW;             fp64 uniforms in [0, 1) handed to every step, 0 <= NW <= 4
+ *   and, with NP > 0,
+ *       static constexpr double PAR_DEFAULT[NP];      the value of a parameter the user does not set
+ *       static constexpr const char* PAR_NAMES;       NP comma-separated identifiers, e.g. "slip,wind"
+ * and its three functions take one trailing argument, `const pgm_env_ctx& c`:
+ *       reset(sd, si, u, c)   observe(sd, si, obs, c)   step(sd, si, action, obj, reward, done, bad, c)
+ * c.par points at the NP parameters in all three.  c.w points at the step's NW uniforms in step and is NULL in reset
+ * and observe.  The parameters are the run's (TaskBatch(env_params={name: value}), --env-param NAME=VALUE): one set for
+ * every task and env, uploaded per launch, so a changed value needs no new library.  They live in registers like the
+ * state words: index c.par and c.w with constants.
+ *
+ * The uniforms are integer hashes, so the host and the device agree bit for bit:
+ *       u53(seed, i) = (double)(splitmix64(key(seed) ^ i) >> 11) * 2^-53
+ * with key the stream key of the action noise (pgm_normal_noise / pgm_uniform_noise).  They never depend on the task:
+ *   training     word j of (step t, env n) of a rollout is element (t N + n) NW + j of the stream of env_seed;
+ *   evaluation   word j of (episode e, step it) is element (e MAX_STEPS + it) NW + j of the stream of env_seed: every
+ *                policy is evaluated under common random numbers.
+ * pgm_envplug_uniforms is that stream on the host.
  */
 #ifndef PGM_ENVPLUG_H
 #define PGM_ENVPLUG_H
@@ -69,6 +93,14 @@
 #define PGM_ENVPLUG_MAX_SD 16
 #define PGM_ENVPLUG_MAX_SI 4
 #define PGM_ENVPLUG_MAX_RW 8
+#define PGM_ENVPLUG_MAX_NP 16
+#define PGM_ENVPLUG_MAX_NW 4
+
+/* contract 2: what reset, observe and step receive beside their own arguments */
+typedef struct pgm_env_ctx {
+    const double* par; /* NP runtime parameters */
+    const double* w;   /* step: NW uniforms in [0, 1); reset, observe: NULL */
+} pgm_env_ctx;
 
 #endif /* PGM_ENVPLUG_H */
 
@@ -120,6 +152,39 @@ int pgm_envplug_transition(int32_t n, const double* sd, const int32_t* si, const
 /* Host only: item i = the start state of entry (row[i], episode[i] mod R) and its observation */
 int pgm_envplug_reset(int32_t n, const int32_t* row, const int32_t* episode, const double* table, int32_t R,
                       int32_t reset_count, double* sd_out, int32_t* si_out, double* obs_out);
+
+/* ---- contract 2.  A library built from a CONTRACT = 2 header refuses the four calls above with PGM_E_UNSUPPORTED and
+ * a message naming the _ex call.  A contract-1 library accepts the _ex calls with env_par = NULL, env_rnd = NULL (w =
+ * NULL) and any seed: they are then the calls above. */
+int pgm_envplug_contract(void); /* 1 or 2 */
+/* out[11] = pgm_envplug_info's 8, then CONTRACT, NP, NW */
+int pgm_envplug_info_ex(int32_t* out);
+/* names: PAR_NAMES ("" with NP = 0) copied into cap bytes, NUL included; defaults: NP values.  Either may be NULL. */
+int pgm_envplug_params(char* names, int32_t cap, double* defaults);
+/* Host only: out[k] = u53(seed, start + k), k < n: the env-noise stream */
+int pgm_envplug_uniforms(uint64_t seed, uint64_t start, int64_t n, double* out);
+
+/* pgm_envplug_rollout with env_par [NP] (device) and the step uniforms env_rnd [T][N][NW] (device), or NULL for
+ * u53(env_seed, (t N + n) NW + j).  Validation: pgm_envplug_rollout's, in its order; then env_par NULL with NP > 0 is
+ * PGM_E_INVALID_ARG.  All of it before any device work. */
+int pgm_envplug_rollout_ex(const pgm_dims* d, const float* params, double* sd, int32_t* si, int32_t* episode,
+                           const double* table, int32_t R, int32_t reset_count, const pgm_env_state* st,
+                           const pgm_norm_state* ns, const pgm_rollout_buf* rb, const float* stream_in, uint64_t seed,
+                           int32_t carry, const double* env_par, const double* env_rnd, uint64_t env_seed,
+                           pgm_stream_t stream);
+/* pgm_envplug_eval with env_par [NP] (device); step `it` of episode e draws u53(env_seed, (e MAX_STEPS + it) NW + j) */
+int pgm_envplug_eval_ex(const pgm_dims* d, const float* params, const double* table, int32_t R, int32_t reset_count,
+                        const double* ob_mean, const double* ob_var, int32_t eval_num, int32_t use_ob_rms, int32_t raw,
+                        double gamma, double* objs_out, const double* env_par, uint64_t env_seed, pgm_stream_t stream);
+/* Host only: pgm_envplug_transition / pgm_envplug_reset with env_par [NP] and (transition) item i's uniforms w [n][NW];
+ * after their own checks, env_par NULL with NP > 0 or w NULL with NW > 0 is PGM_E_INVALID_ARG */
+int pgm_envplug_transition_ex(int32_t n, const double* sd, const int32_t* si, const int32_t* elapsed,
+                              const int32_t* episode, const int32_t* row, const void* action, const double* table,
+                              int32_t R, int32_t reset_count, const double* env_par, const double* w, double* sd_out,
+                              int32_t* si_out, int32_t* elapsed_out, int32_t* episode_out, double* obs_out,
+                              double* obj_out, double* reward_out, int32_t* done_out, int32_t* bad_out);
+int pgm_envplug_reset_ex(int32_t n, const int32_t* row, const int32_t* episode, const double* table, int32_t R,
+                         int32_t reset_count, const double* env_par, double* sd_out, int32_t* si_out, double* obs_out);
 
 #ifdef __cplusplus
 }

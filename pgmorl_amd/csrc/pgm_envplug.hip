@@ -21,6 +21,7 @@
 
 #include <stdarg.h>
 #include <stdio.h>
+#include <string.h>
 
 #define PGM_ENVPLUG_EXPORT extern "C"
 
@@ -77,6 +78,12 @@ using envplug::SIN;
 constexpr int EO = Env::O, EA = Env::A, EK = Env::K;
 constexpr bool CAT = Env::DISCRETE;
 constexpr int AW = CAT ? 1 : EA;  // stored action width, random inputs per (step, env)
+// contract 2 (runtime parameters, per-step uniforms); for a contract-1 header every use below is compiled out
+using envplug::C2;
+using envplug::NP;
+using envplug::NPN;
+using envplug::NW;
+using envplug::NWN;
 
 // the step image of the block kernels plus the scalar env reward of the step (VecNormalize.ret's input)
 struct PlugSmem {
@@ -98,6 +105,10 @@ struct PlugRolloutArgs {
     const float* rnd;  // normals [T][N][A] / uniforms [T][N], or NULL: the counter stream of seed
     uint64_t seed;
     int carry;
+    // contract 2
+    const double* env_par;  // [NP]
+    const double* env_rnd;  // [T][N][NW], or NULL: u53 of env_seed
+    uint64_t env_seed;
 };
 
 __device__ __forceinline__ float plug_draw(const PlugRolloutArgs& a, size_t idx) {
@@ -106,6 +117,11 @@ __device__ __forceinline__ float plug_draw(const PlugRolloutArgs& a, size_t idx)
     } else {
         return a.rnd ? a.rnd[idx] : counter_normal(a.seed, idx);
     }
+}
+
+// word j of (step, env) of the rollout's env noise: element (step N + n) NW + j
+__device__ __forceinline__ double plug_draw_env(const PlugRolloutArgs& a, uint64_t key, size_t idx) {
+    return a.env_rnd ? a.env_rnd[idx] : envplug::u53_at(key, idx);
 }
 
 __device__ __forceinline__ void plug_load(envplug::State& s, const PlugRolloutArgs& a, int g) {
@@ -128,7 +144,8 @@ __device__ __forceinline__ void plug_store(const envplug::State& s, const PlugRo
 // fused rollout.  Thread n < N owns env n: it keeps the env's state words in registers, draws the env's random inputs
 // one step ahead, samples its action (sample_actions' / CatHead's arithmetic) and runs its transition.  Four
 // workgroup barriers per step: policy_forward, the transition hand-off, norm_stats, vecnorm_emit.  Every loop is
-// bounded by T + 1, N or a compile-time constant.
+// bounded by T + 1, N or a compile-time constant.  Contract 2: every thread holds the NP parameters (one address, a
+// scalar load) and the owner draws the step's NW uniforms where it draws the action noise, one step ahead.
 __global__ __launch_bounds__(RT) void rollout_env_kernel(PlugRolloutArgs a, Layout L) {
     constexpr int O = EO, A = EA, K = EK;
     extern __shared__ __attribute__((aligned(16))) char smem_raw[];
@@ -152,6 +169,13 @@ __global__ __launch_bounds__(RT) void rollout_env_kernel(PlugRolloutArgs a, Layo
     load_env<false>(E, a.st, a.ns, p, N);
     envplug::State env = {};
     if (owner) plug_load(env, a, p * N + t);
+    double par[NPN] = {}, w[NWN] = {}, w_next[NWN] = {};
+    uint64_t env_key = 0;
+    if constexpr (C2) {
+#pragma unroll
+        for (int i = 0; i < NP; ++i) par[i] = a.env_par[i];
+        if constexpr (NW > 0) env_key = envplug::noise_key(a.env_seed);
+    }
     const double* row = a.table + (size_t)(owner ? t : 0) * a.R * Env::RW;
     if (a.carry) {  // after_update(): slot T -> slot 0 (storage.py:71-75); each thread re-reads its own writes
         for (int i = t; i < N * O; i += RT) obs[i] = obs[(size_t)T * N * O + i];
@@ -174,6 +198,10 @@ __global__ __launch_bounds__(RT) void rollout_env_kernel(PlugRolloutArgs a, Layo
     if (owner) {
 #pragma unroll
         for (int j = 0; j < AW; ++j) rnd_next[j] = plug_draw(a, (size_t)(t * AW + j));
+        if constexpr (C2) {
+#pragma unroll
+            for (int j = 0; j < NW; ++j) w_next[j] = plug_draw_env(a, env_key, (size_t)(t * NW + j));
+        }
     }
     PGM_STAMP_DECL
     // T + 1 passes: the last one is the bootstrap value alone (mopg.py:132-135 -> value_preds[T], storage.py:85).  It
@@ -183,9 +211,18 @@ __global__ __launch_bounds__(RT) void rollout_env_kernel(PlugRolloutArgs a, Layo
         float rnd[EA];
 #pragma unroll
         for (int j = 0; j < AW; ++j) rnd[j] = rnd_next[j];
+        if constexpr (C2) {
+#pragma unroll
+            for (int j = 0; j < NW; ++j) w[j] = w_next[j];
+        }
         if (owner && step + 1 < T) {
 #pragma unroll
             for (int j = 0; j < AW; ++j) rnd_next[j] = plug_draw(a, ((size_t)(step + 1) * N + t) * AW + j);
+            if constexpr (C2) {
+#pragma unroll
+                for (int j = 0; j < NW; ++j)
+                    w_next[j] = plug_draw_env(a, env_key, ((size_t)(step + 1) * N + t) * NW + j);
+            }
         }
         PGM_STAMP(0);
         policy_forward<PlainTowers>(P, R, N, prm, L);
@@ -194,12 +231,13 @@ __global__ __launch_bounds__(RT) void rollout_env_kernel(PlugRolloutArgs a, Layo
         if (step == T) break;  // uniform over the workgroup
         if (owner) {
             envplug::StepOut o;
+            const pgm_env_ctx ctx{par, w};
             if constexpr (CAT) {
                 float lp;
                 const int ai = cat_sample<A>(P.mu[t], false, rnd[0], lp);
                 act[(size_t)step * N + t] = (float)ai;
                 logp[(size_t)step * N + t] = lp;
-                o = envplug::transition(env, envplug::Action{nullptr, ai}, row, a.R);
+                o = envplug::transition(env, envplug::Action{nullptr, ai}, row, a.R, ctx);
             } else {
                 float av[A], lp = 0.f;
 #pragma unroll
@@ -210,9 +248,9 @@ __global__ __launch_bounds__(RT) void rollout_env_kernel(PlugRolloutArgs a, Layo
                     act[((size_t)step * N + t) * A + j] = av[j];  // raw, unclipped: the env clips
                 }
                 logp[(size_t)step * N + t] = lp;
-                o = envplug::transition(env, envplug::Action{av, 0}, row, a.R);
+                o = envplug::transition(env, envplug::Action{av, 0}, row, a.R, ctx);
             }
-            Env::observe(env.sd, env.si, E.snew[t]);
+            envplug::call_observe<Env>(env.sd, env.si, E.snew[t], par);
 #pragma unroll
             for (int k = 0; k < K; ++k) E.objraw[t][k] = o.obj[k];
             E.done[t] = o.done;
@@ -242,6 +280,9 @@ struct PlugEvalArgs {
     int eval_num, use_ob, raw;
     double gamma;
     double* objs;
+    // contract 2
+    const double* env_par;  // [NP]
+    uint64_t env_seed;      // word j of (episode e, step it): element (e MAX_STEPS + it) NW + j
 };
 
 // deterministic evaluation (mopg.py:25-46): eval_num episodes are the rows of one forward and step together; thread
@@ -265,13 +306,36 @@ __global__ __launch_bounds__(RT) void eval_env_kernel(PlugEvalArgs a, Layout L) 
     envplug::State env = {};
     int alive = 1;
     double acc[K] = {}, disc = 1.0;
+    double par[NPN] = {}, w[NWN] = {}, w_next[NWN] = {};
+    uint64_t env_key = 0;
+    if constexpr (C2) {
+#pragma unroll
+        for (int i = 0; i < NP; ++i) par[i] = a.env_par[i];
+        if constexpr (NW > 0) {
+            env_key = envplug::noise_key(a.env_seed);
+            if (owner) {
+#pragma unroll
+                for (int j = 0; j < NW; ++j)
+                    w_next[j] = envplug::u53_at(env_key, (size_t)t * Env::MAX_STEPS * NW + j);
+            }
+        }
+    }
     if (owner) {
-        envplug::start(env, a.table + (size_t)t * a.R * Env::RW);
-        Env::observe(env.sd, env.si, E.snew[t]);
+        envplug::start(env, a.table + (size_t)t * a.R * Env::RW, pgm_env_ctx{par, nullptr});
+        envplug::call_observe<Env>(env.sd, env.si, E.snew[t], par);
         E.done[t] = 0;
     }
     __syncthreads();
     for (int it = 0; it < Env::MAX_STEPS; ++it) {
+        if constexpr (C2 && NW > 0) {  // this step's uniforms; the next step's are drawn beside the forward
+#pragma unroll
+            for (int j = 0; j < NW; ++j) w[j] = w_next[j];
+            if (owner && alive && it + 1 < Env::MAX_STEPS) {
+#pragma unroll
+                for (int j = 0; j < NW; ++j)
+                    w_next[j] = envplug::u53_at(env_key, ((size_t)t * Env::MAX_STEPS + it + 1) * NW + j);
+            }
+        }
         for (int i = t; i < EN * O; i += RT) {
             const int e = i / O, o = i % O;
             P.x[e][o] = eval_normalise(E.snew[e][o], a.use_ob, E.ob_mean[o], E.ob_inv[o]);
@@ -280,14 +344,15 @@ __global__ __launch_bounds__(RT) void eval_env_kernel(PlugEvalArgs a, Layout L) 
         policy_forward<PlainTowers>(P, R, EN, prm, L);
         if (owner && alive) {  // the mean action (the env clips it) / the lowest-index argmax
             envplug::StepOut o;
+            const pgm_env_ctx ctx{par, w};
             if constexpr (CAT) {
                 float lp;
-                o = envplug::step_limit(env, envplug::Action{nullptr, cat_sample<A>(P.mu[t], true, 0.f, lp)});
+                o = envplug::step_limit(env, envplug::Action{nullptr, cat_sample<A>(P.mu[t], true, 0.f, lp)}, ctx);
             } else {
                 float av[A];
 #pragma unroll
                 for (int j = 0; j < A; ++j) av[j] = P.mu[t][j];
-                o = envplug::step_limit(env, envplug::Action{av, 0});
+                o = envplug::step_limit(env, envplug::Action{av, 0}, ctx);
             }
 #pragma unroll
             for (int k = 0; k < K; ++k) acc[k] += disc * o.obj[k];
@@ -295,7 +360,7 @@ __global__ __launch_bounds__(RT) void eval_env_kernel(PlugEvalArgs a, Layout L) 
                 alive = 0;
                 E.done[t] = 1;
             } else {
-                Env::observe(env.sd, env.si, E.snew[t]);
+                envplug::call_observe<Env>(env.sd, env.si, E.snew[t], par);
             }
         }
         if (!a.raw) disc *= a.gamma;
@@ -345,6 +410,21 @@ static int check_plug_table(int R, int reset_count, int need, const char* what) 
     return PGM_OK;
 }
 
+// a library built from a CONTRACT = 2 header answers the calls without env_par / env noise with this
+static int refuse_contract2(const char* what) {
+    set_error("%s: this library is built from a CONTRACT = 2 header (NP = %d runtime parameters, NW = %d uniforms per "
+              "step): call %s_ex", what, NP, NW, what);
+    return PGM_E_UNSUPPORTED;
+}
+// after every check of the contract-1 call
+static int check_env_par(const double* env_par, const char* what) {
+    if (NP > 0 && !env_par) {
+        set_error("%s: env_par is a null pointer, the header has NP = %d runtime parameters", what, NP);
+        return PGM_E_INVALID_ARG;
+    }
+    return PGM_OK;
+}
+
 }  // namespace pgm
 
 using namespace pgm;
@@ -362,12 +442,11 @@ PGM_ENVPLUG_EXPORT int pgm_envplug_info(int32_t* out) {
     return PGM_OK;
 }
 
-PGM_ENVPLUG_EXPORT int pgm_envplug_rollout(const pgm_dims* d, const float* params, double* sd, int32_t* si,
-                                           int32_t* episode, const double* table, int32_t R, int32_t reset_count,
-                                           const pgm_env_state* st, const pgm_norm_state* ns,
-                                           const pgm_rollout_buf* rb, const float* stream_in, uint64_t seed,
-                                           int32_t carry, pgm_stream_t stream) {
-    const char* what = "pgm_envplug_rollout";
+static int plug_rollout(const char* what, const pgm_dims* d, const float* params, double* sd, int32_t* si,
+                        int32_t* episode, const double* table, int32_t R, int32_t reset_count,
+                        const pgm_env_state* st, const pgm_norm_state* ns, const pgm_rollout_buf* rb,
+                        const float* stream_in, uint64_t seed, int32_t carry, const double* env_par,
+                        const double* env_rnd, uint64_t env_seed, pgm_stream_t stream) {
     if (!d || !params || (Env::SD > 0 && !sd) || (Env::SI > 0 && !si) || !episode || (Env::RW > 0 && !table) || !st ||
         !st->elapsed || !st->obj_acc || !st->obj_acc_valid || !st->ret || !norm_ok(ns) || !rb || !rb->obs ||
         !rb->actions || !rb->logp || !rb->values || !rb->rewards || !rb->masks || !rb->bad_masks) {
@@ -381,15 +460,36 @@ PGM_ENVPLUG_EXPORT int pgm_envplug_rollout(const pgm_dims* d, const float* param
         return PGM_E_SHAPE;
     }
     if (int rc = check_plug_table(R, reset_count, d->N, what)) return rc;
-    PlugRolloutArgs a{d->P, d->N, d->T, params, sd, si, episode, table, R, *st, *ns, *rb, stream_in, seed, carry};
+    if (int rc = check_env_par(env_par, what)) return rc;
+    PlugRolloutArgs a{d->P, d->N, d->T, params, sd, si, episode, table, R, *st, *ns, *rb, stream_in, seed, carry,
+                      C2 ? env_par : nullptr, C2 && NW > 0 ? env_rnd : nullptr, env_seed};
     return launch_smem(rollout_env_kernel, d->P, sizeof(PlugSmem), (hipStream_t)stream, what, a, plug_layout());
 }
 
-PGM_ENVPLUG_EXPORT int pgm_envplug_eval(const pgm_dims* d, const float* params, const double* table, int32_t R,
-                                        int32_t reset_count, const double* ob_mean, const double* ob_var,
-                                        int32_t eval_num, int32_t use_ob_rms, int32_t raw, double gamma,
-                                        double* objs_out, pgm_stream_t stream) {
-    const char* what = "pgm_envplug_eval";
+PGM_ENVPLUG_EXPORT int pgm_envplug_rollout(const pgm_dims* d, const float* params, double* sd, int32_t* si,
+                                           int32_t* episode, const double* table, int32_t R, int32_t reset_count,
+                                           const pgm_env_state* st, const pgm_norm_state* ns,
+                                           const pgm_rollout_buf* rb, const float* stream_in, uint64_t seed,
+                                           int32_t carry, pgm_stream_t stream) {
+    if (C2) return refuse_contract2("pgm_envplug_rollout");
+    return plug_rollout("pgm_envplug_rollout", d, params, sd, si, episode, table, R, reset_count, st, ns, rb, stream_in,
+                        seed, carry, nullptr, nullptr, 0, stream);
+}
+
+PGM_ENVPLUG_EXPORT int pgm_envplug_rollout_ex(const pgm_dims* d, const float* params, double* sd, int32_t* si,
+                                              int32_t* episode, const double* table, int32_t R, int32_t reset_count,
+                                              const pgm_env_state* st, const pgm_norm_state* ns,
+                                              const pgm_rollout_buf* rb, const float* stream_in, uint64_t seed,
+                                              int32_t carry, const double* env_par, const double* env_rnd,
+                                              uint64_t env_seed, pgm_stream_t stream) {
+    return plug_rollout("pgm_envplug_rollout_ex", d, params, sd, si, episode, table, R, reset_count, st, ns, rb,
+                        stream_in, seed, carry, env_par, env_rnd, env_seed, stream);
+}
+
+static int plug_eval(const char* what, const pgm_dims* d, const float* params, const double* table, int32_t R,
+                     int32_t reset_count, const double* ob_mean, const double* ob_var, int32_t eval_num,
+                     int32_t use_ob_rms, int32_t raw, double gamma, double* objs_out, const double* env_par,
+                     uint64_t env_seed, pgm_stream_t stream) {
     if (!d || !params || (Env::RW > 0 && !table) || !objs_out || (use_ob_rms && (!ob_mean || !ob_var))) {
         set_error("%s: null pointer (ob_mean / ob_var are required with use_ob_rms)", what);
         return PGM_E_INVALID_ARG;
@@ -404,18 +504,36 @@ PGM_ENVPLUG_EXPORT int pgm_envplug_eval(const pgm_dims* d, const float* params, 
         return PGM_E_INVALID_ARG;
     }
     if (int rc = check_plug_table(R, reset_count, eval_num, what)) return rc;
-    PlugEvalArgs a{d->P, params, table, R, ob_mean, ob_var, eval_num, use_ob_rms != 0, raw != 0, gamma, objs_out};
+    if (int rc = check_env_par(env_par, what)) return rc;
+    PlugEvalArgs a{d->P,   params, table, R, ob_mean, ob_var, eval_num, use_ob_rms != 0, raw != 0, gamma, objs_out,
+                   C2 ? env_par : nullptr, env_seed};
     return launch_smem(eval_env_kernel, d->P, sizeof(PlugSmem), (hipStream_t)stream, what, a, plug_layout());
 }
 
+PGM_ENVPLUG_EXPORT int pgm_envplug_eval(const pgm_dims* d, const float* params, const double* table, int32_t R,
+                                        int32_t reset_count, const double* ob_mean, const double* ob_var,
+                                        int32_t eval_num, int32_t use_ob_rms, int32_t raw, double gamma,
+                                        double* objs_out, pgm_stream_t stream) {
+    if (C2) return refuse_contract2("pgm_envplug_eval");
+    return plug_eval("pgm_envplug_eval", d, params, table, R, reset_count, ob_mean, ob_var, eval_num, use_ob_rms, raw,
+                     gamma, objs_out, nullptr, 0, stream);
+}
+
+PGM_ENVPLUG_EXPORT int pgm_envplug_eval_ex(const pgm_dims* d, const float* params, const double* table, int32_t R,
+                                           int32_t reset_count, const double* ob_mean, const double* ob_var,
+                                           int32_t eval_num, int32_t use_ob_rms, int32_t raw, double gamma,
+                                           double* objs_out, const double* env_par, uint64_t env_seed,
+                                           pgm_stream_t stream) {
+    return plug_eval("pgm_envplug_eval_ex", d, params, table, R, reset_count, ob_mean, ob_var, eval_num, use_ob_rms,
+                     raw, gamma, objs_out, env_par, env_seed, stream);
+}
+
 // Host only: launches nothing and needs no device.
-PGM_ENVPLUG_EXPORT int pgm_envplug_transition(int32_t n, const double* sd, const int32_t* si, const int32_t* elapsed,
-                                              const int32_t* episode, const int32_t* row, const void* action,
-                                              const double* table, int32_t R, int32_t reset_count, double* sd_out,
-                                              int32_t* si_out, int32_t* elapsed_out, int32_t* episode_out,
-                                              double* obs_out, double* obj_out, double* reward_out, int32_t* done_out,
-                                              int32_t* bad_out) {
-    const char* what = "pgm_envplug_transition";
+static int plug_transition(const char* what, int32_t n, const double* sd, const int32_t* si, const int32_t* elapsed,
+                           const int32_t* episode, const int32_t* row, const void* action, const double* table,
+                           int32_t R, int32_t reset_count, const double* env_par, const double* w, double* sd_out,
+                           int32_t* si_out, int32_t* elapsed_out, int32_t* episode_out, double* obs_out,
+                           double* obj_out, double* reward_out, int32_t* done_out, int32_t* bad_out) {
     if (n < 0 || (Env::SD > 0 && (!sd || !sd_out)) || (Env::SI > 0 && (!si || !si_out)) || !elapsed || !episode ||
         !row || !action || (Env::RW > 0 && !table) || !elapsed_out || !episode_out || !obs_out || !obj_out ||
         !reward_out || !done_out || !bad_out) {
@@ -434,7 +552,13 @@ PGM_ENVPLUG_EXPORT int pgm_envplug_transition(int32_t n, const double* sd, const
             return PGM_E_INVALID_ARG;
         }
     }
+    if (int rc = check_env_par(env_par, what)) return rc;
+    if (NW > 0 && !w) {
+        set_error("%s: w is a null pointer, the header takes NW = %d uniforms per step", what, NW);
+        return PGM_E_INVALID_ARG;
+    }
     for (int32_t i = 0; i < n; ++i) {
+        const pgm_env_ctx ctx{C2 ? env_par : nullptr, C2 && NW > 0 ? w + (size_t)i * NW : nullptr};
         envplug::State s = {};
         for (int j = 0; j < Env::SD; ++j) s.sd[j] = sd[(size_t)i * Env::SD + j];
         for (int j = 0; j < Env::SI; ++j) s.si[j] = si[(size_t)i * Env::SI + j];
@@ -443,15 +567,15 @@ PGM_ENVPLUG_EXPORT int pgm_envplug_transition(int32_t n, const double* sd, const
         const double* rp = table + (size_t)row[i] * R * Env::RW;
         envplug::StepOut o;
         if (CAT) {
-            o = envplug::transition(s, envplug::Action{nullptr, (int)((const int32_t*)action)[i]}, rp, R);
+            o = envplug::transition(s, envplug::Action{nullptr, (int)((const int32_t*)action)[i]}, rp, R, ctx);
         } else {
-            o = envplug::transition(s, envplug::Action{(const float*)action + (size_t)i * EA, 0}, rp, R);
+            o = envplug::transition(s, envplug::Action{(const float*)action + (size_t)i * EA, 0}, rp, R, ctx);
         }
         for (int j = 0; j < Env::SD; ++j) sd_out[(size_t)i * Env::SD + j] = s.sd[j];
         for (int j = 0; j < Env::SI; ++j) si_out[(size_t)i * Env::SI + j] = s.si[j];
         elapsed_out[i] = s.elapsed;
         episode_out[i] = s.episode;
-        Env::observe(s.sd, s.si, obs_out + (size_t)i * EO);
+        envplug::call_observe<Env>(s.sd, s.si, obs_out + (size_t)i * EO, ctx.par);
         for (int k = 0; k < EK; ++k) obj_out[(size_t)i * EK + k] = o.obj[k];
         reward_out[i] = o.reward;
         done_out[i] = o.done;
@@ -460,10 +584,33 @@ PGM_ENVPLUG_EXPORT int pgm_envplug_transition(int32_t n, const double* sd, const
     return PGM_OK;
 }
 
-PGM_ENVPLUG_EXPORT int pgm_envplug_reset(int32_t n, const int32_t* row, const int32_t* episode, const double* table,
-                                         int32_t R, int32_t reset_count, double* sd_out, int32_t* si_out,
-                                         double* obs_out) {
-    const char* what = "pgm_envplug_reset";
+PGM_ENVPLUG_EXPORT int pgm_envplug_transition(int32_t n, const double* sd, const int32_t* si, const int32_t* elapsed,
+                                              const int32_t* episode, const int32_t* row, const void* action,
+                                              const double* table, int32_t R, int32_t reset_count, double* sd_out,
+                                              int32_t* si_out, int32_t* elapsed_out, int32_t* episode_out,
+                                              double* obs_out, double* obj_out, double* reward_out, int32_t* done_out,
+                                              int32_t* bad_out) {
+    if (C2) return refuse_contract2("pgm_envplug_transition");
+    return plug_transition("pgm_envplug_transition", n, sd, si, elapsed, episode, row, action, table, R, reset_count,
+                           nullptr, nullptr, sd_out, si_out, elapsed_out, episode_out, obs_out, obj_out, reward_out,
+                           done_out, bad_out);
+}
+
+PGM_ENVPLUG_EXPORT int pgm_envplug_transition_ex(int32_t n, const double* sd, const int32_t* si,
+                                                 const int32_t* elapsed, const int32_t* episode, const int32_t* row,
+                                                 const void* action, const double* table, int32_t R,
+                                                 int32_t reset_count, const double* env_par, const double* w,
+                                                 double* sd_out, int32_t* si_out, int32_t* elapsed_out,
+                                                 int32_t* episode_out, double* obs_out, double* obj_out,
+                                                 double* reward_out, int32_t* done_out, int32_t* bad_out) {
+    return plug_transition("pgm_envplug_transition_ex", n, sd, si, elapsed, episode, row, action, table, R,
+                           reset_count, env_par, w, sd_out, si_out, elapsed_out, episode_out, obs_out, obj_out,
+                           reward_out, done_out, bad_out);
+}
+
+static int plug_reset(const char* what, int32_t n, const int32_t* row, const int32_t* episode, const double* table,
+                      int32_t R, int32_t reset_count, const double* env_par, double* sd_out, int32_t* si_out,
+                      double* obs_out) {
     if (n < 0 || !row || !episode || (Env::RW > 0 && !table) || (Env::SD > 0 && !sd_out) || (Env::SI > 0 && !si_out) ||
         !obs_out) {
         set_error("%s: null pointer or negative n", what);
@@ -476,12 +623,67 @@ PGM_ENVPLUG_EXPORT int pgm_envplug_reset(int32_t n, const int32_t* row, const in
                       reset_count, episode[i]);
             return PGM_E_INVALID_ARG;
         }
+    if (int rc = check_env_par(env_par, what)) return rc;
+    const pgm_env_ctx ctx{C2 ? env_par : nullptr, nullptr};
     for (int32_t i = 0; i < n; ++i) {
         envplug::State s = {};
-        envplug::start(s, table + ((size_t)row[i] * R + episode[i] % R) * Env::RW);
+        envplug::start(s, table + ((size_t)row[i] * R + episode[i] % R) * Env::RW, ctx);
         for (int j = 0; j < Env::SD; ++j) sd_out[(size_t)i * Env::SD + j] = s.sd[j];
         for (int j = 0; j < Env::SI; ++j) si_out[(size_t)i * Env::SI + j] = s.si[j];
-        Env::observe(s.sd, s.si, obs_out + (size_t)i * EO);
+        envplug::call_observe<Env>(s.sd, s.si, obs_out + (size_t)i * EO, ctx.par);
     }
+    return PGM_OK;
+}
+
+PGM_ENVPLUG_EXPORT int pgm_envplug_reset(int32_t n, const int32_t* row, const int32_t* episode, const double* table,
+                                         int32_t R, int32_t reset_count, double* sd_out, int32_t* si_out,
+                                         double* obs_out) {
+    if (C2) return refuse_contract2("pgm_envplug_reset");
+    return plug_reset("pgm_envplug_reset", n, row, episode, table, R, reset_count, nullptr, sd_out, si_out, obs_out);
+}
+
+PGM_ENVPLUG_EXPORT int pgm_envplug_reset_ex(int32_t n, const int32_t* row, const int32_t* episode, const double* table,
+                                            int32_t R, int32_t reset_count, const double* env_par, double* sd_out,
+                                            int32_t* si_out, double* obs_out) {
+    return plug_reset("pgm_envplug_reset_ex", n, row, episode, table, R, reset_count, env_par, sd_out, si_out, obs_out);
+}
+
+// ---- contract 2: what the header declares, and the env-noise stream on the host
+PGM_ENVPLUG_EXPORT int pgm_envplug_contract(void) { return envplug::CONTRACT; }
+
+PGM_ENVPLUG_EXPORT int pgm_envplug_info_ex(int32_t* out) {
+    if (!out) {
+        set_error("pgm_envplug_info_ex: null pointer");
+        return PGM_E_INVALID_ARG;
+    }
+    if (int rc = pgm_envplug_info(out)) return rc;
+    out[8] = envplug::CONTRACT;
+    out[9] = NP;
+    out[10] = NW;
+    return PGM_OK;
+}
+
+PGM_ENVPLUG_EXPORT int pgm_envplug_params(char* names, int32_t cap, double* defaults) {
+    const char* text = NP > 0 ? envplug::names_of<Env>::text : "";
+    if (names) {
+        const size_t len = strlen(text);
+        if (cap < 0 || (size_t)cap < len + 1) {
+            set_error("pgm_envplug_params: cap = %d bytes, the names need %d", cap, (int)len + 1);
+            return PGM_E_INVALID_ARG;
+        }
+        memcpy(names, text, len + 1);
+    }
+    if (defaults)
+        for (int i = 0; i < NP; ++i) defaults[i] = envplug::defaults_of<Env>::at(i);
+    return PGM_OK;
+}
+
+PGM_ENVPLUG_EXPORT int pgm_envplug_uniforms(uint64_t seed, uint64_t start, int64_t n, double* out) {
+    if (n < 0 || (n > 0 && !out)) {
+        set_error("pgm_envplug_uniforms: null pointer or negative n");
+        return PGM_E_INVALID_ARG;
+    }
+    const uint64_t key = envplug::noise_key(seed);
+    for (int64_t k = 0; k < n; ++k) out[k] = envplug::u53_at(key, start + (uint64_t)k);
     return PGM_OK;
 }

@@ -338,12 +338,22 @@ class PluginHostVecEnv(HostVecEnv):
     forced step limit and the auto-reset.  The reference point of the fused path (for a header without transcendentals
     the two agree bit for bit) and a debugging path for the header's author.  Env n of every task uses row n of
     envspec.plugin_reset_table(seed, N, R, RW); evaluation episode e starts at entry (e, 0) of the eval_num-row
-    table."""
+    table.
 
-    def __init__(self, plugin, P, N, seed=0, R=None):
+    A contract-2 header gets what the fused kernels give it: the runtime parameters ``env_params`` (a dict over the
+    header's names; omitted names take the default) and, per step, the uniforms of the env-noise stream at the fused
+    path's indices -- training word j of (step t, env n): element (t N + n) NW + j of the rollout's env_seed
+    (``begin_rollout``, which restarts t); evaluation word j of (episode e, step it): element (e MAX_STEPS + it) NW + j
+    of envplug.env_seed(seed)."""
+
+    def __init__(self, plugin, P, N, seed=0, R=None, env_params=None):
         from . import envplug
         self.plugin = pl = envplug.as_plugin(plugin)
+        self.par = pl.par_vector(env_params)
         self.seed = seed
+        self._env_seed = self._eval_env_seed = envplug.env_seed(seed)
+        self._env_noise = None
+        self._t = self._et = 0
         self.capacity = self.P = P
         self.N = N
         self.obs_dim, self.act_dim, self.obj_num = pl.O, pl.A, pl.K
@@ -361,8 +371,32 @@ class PluginHostVecEnv(HostVecEnv):
     def _fresh(self, P, M, table):
         row = np.broadcast_to(np.arange(M, dtype=np.int32), (P, M)).reshape(-1).copy()
         zero = np.zeros(P * M, dtype=np.int32)
-        sd, si, obs = self.plugin.reset(row, zero, table)
+        sd, si, obs = self.plugin.reset(row, zero, table, par=self.par)
         return {'sd': sd, 'si': si, 'elapsed': zero.copy(), 'episode': zero.copy(), 'row': row}, obs
+
+    def begin_rollout(self, env_seed, env_noise=None):
+        """The env noise of the rollout that starts now: the stream of ``env_seed`` from step 0, or the fed uniforms
+        ``env_noise`` [T][N][NW] (what pgm_envplug_rollout_ex takes as env_rnd)."""
+        self._env_seed, self._t = int(env_seed), 0
+        self._env_noise = None if env_noise is None else np.asarray(env_noise, dtype=np.float64)
+
+    def _train_w(self):
+        """[P N][NW]: step t's uniforms of env n, the same for every task; None for a header without them."""
+        NW, N = self.plugin.NW, self.N
+        if NW == 0:
+            return None
+        if self._env_noise is not None:
+            w = self._env_noise[self._t].reshape(N, NW)
+        else:
+            w = self.plugin.uniforms(self._env_seed, self._t * N * NW, N * NW).reshape(N, NW)
+        return np.broadcast_to(w, (self.P, N, NW)).reshape(-1, NW)
+
+    def _eval_w(self, E):
+        NW, L = self.plugin.NW, self.plugin.MAX_STEPS
+        if NW == 0:
+            return None
+        w = np.stack([self.plugin.uniforms(self._eval_env_seed, (e * L + self._et) * NW, NW) for e in range(E)])
+        return np.broadcast_to(w, (self.P, E, NW)).reshape(-1, NW)
 
     def _action(self, actions):
         if self.discrete:
@@ -371,12 +405,14 @@ class PluginHostVecEnv(HostVecEnv):
 
     def reset(self):
         self._st, obs = self._fresh(self.P, self.N, self.table)
+        self._t = 0
         return obs.reshape(self.P, self.N, self.obs_dim)
 
     def step(self, actions):
         st, P, N = self._st, self.P, self.N
         o = self.plugin.transition(st['sd'], st['si'], st['elapsed'], st['episode'], st['row'],
-                                   self._action(actions), self.table)
+                                   self._action(actions), self.table, par=self.par, w=self._train_w())
+        self._t += 1
         for k in ('sd', 'si', 'elapsed', 'episode'):
             st[k] = o[k]
         return (o['obs'].reshape(P, N, self.obs_dim), o['reward'].reshape(P, N), o['done'].reshape(P, N).astype(bool),
@@ -387,6 +423,7 @@ class PluginHostVecEnv(HostVecEnv):
         self._est, obs = self._fresh(self.P, eval_num, self._etable)
         self._edone = np.zeros(self.P * eval_num, dtype=bool)
         self._eobs = obs
+        self._et = 0
         return obs.reshape(self.P, eval_num, self.obs_dim).copy()
 
     def eval_step(self, actions):
@@ -395,7 +432,9 @@ class PluginHostVecEnv(HostVecEnv):
         act = self._action(actions)
         if self.discrete:  # an ended episode's action is not looked at (and may be anything)
             act = np.where(self._edone, 0, act).astype(np.int32)
-        o = self.plugin.transition(st['sd'], st['si'], st['elapsed'], st['episode'], st['row'], act, self._etable)
+        o = self.plugin.transition(st['sd'], st['si'], st['elapsed'], st['episode'], st['row'], act, self._etable,
+                                   par=self.par, w=self._eval_w(E))
+        self._et += 1
         live = ~self._edone  # ended episodes stand still
         for k in ('sd', 'si', 'elapsed', 'episode'):
             m = live.reshape((-1,) + (1,) * (o[k].ndim - 1))

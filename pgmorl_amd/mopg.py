@@ -68,7 +68,9 @@ class MOPGPopulation:
         flag): a discrete-action env runs on the device (TaskBatch(device_env=True)); a no-op on the SynthMO envs.
         env_plugin (default ``args.env_plugin``, the --env-plugin flag): an envplug.EnvPlugin or the path of its header;
         every TaskBatch of this runtime runs the plug-in's fused kernels (the library is loaded once and reused when the
-        batch is re-allocated at a larger capacity), or, with host_env 'plugin', steps the same header on the host."""
+        batch is re-allocated at a larger capacity), or, with host_env 'plugin', steps the same header on the host.
+        ``args.env_params`` (the --env-param flags, a dict name -> float) are the runtime parameters of a contract-2
+        plug-in on either path."""
         self.args = args
         self.device = torch.device(device)
         self.rng = rng
@@ -84,8 +86,9 @@ class MOPGPopulation:
             if self.env_plugin is None:
                 raise ValueError('host_env "plugin" steps an env plug-in on the host: give env_plugin=...')
             from .hostenv import PluginHostVecEnv
-            plugin = self.env_plugin
-            host_env = lambda env_name, P, N, seed=0: PluginHostVecEnv(plugin, P, N, seed)  # noqa: E731
+            plugin, env_params = self.env_plugin, getattr(args, 'env_params', None)
+            host_env = lambda env_name, P, N, seed=0: PluginHostVecEnv(plugin, P, N, seed,  # noqa: E731
+                                                                       env_params=env_params)
         if isinstance(host_env, str):
             from .hostenv import resolve
             host_env = resolve(host_env)
@@ -150,7 +153,8 @@ class MOPGPopulation:
                                 entropy_coef=a.entropy_coef, max_grad_norm=a.max_grad_norm, device=self.device,
                                 capacity=cap, layernorm=bool(getattr(a, 'layernorm', False)), host_env=he,
                                 device_env=self.device_env,
-                                env_plugin=self.env_plugin if he is None else None, run_seeds=self.run_seeds)
+                                env_plugin=self.env_plugin if he is None else None, run_seeds=self.run_seeds,
+                                env_params=getattr(a, 'env_params', None) if he is None else None)
         else:
             self.tb.set_active(P)
         return self.tb

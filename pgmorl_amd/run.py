@@ -5,7 +5,8 @@
 Adds ``--rng {device,host}`` (device counter streams, or the reference's own torch draws for
 bit-compatible runs), ``--device``, ``--host-env SPEC`` (environments stepped on the host, hostenv.py) and
 ``--device-env`` (a discrete-action env, Deep Sea Treasure, stepped on the device instead) and ``--env-plugin HEADER``
-(a user env stated as a C++ header, include/pgm_envplug.h, compiled into fused rollout and evaluation kernels).
+(a user env stated as a C++ header, include/pgm_envplug.h, compiled into fused rollout and evaluation kernels), with
+``--env-param NAME=VALUE`` for the runtime parameters of a header under contract 2.
 """
 import argparse
 import os
@@ -74,6 +75,9 @@ def get_parser():
         help='train on a user env stated as one C++ header (include/pgm_envplug.h): the header is compiled into a '
              'fused rollout and evaluation kernel of its own; --env-name is then any name envspec does not know.  '
              'With "--host-env plugin" the same compiled header is stepped on the host instead')
+    add('--env-param', action='append', default=None, metavar='NAME=VALUE',
+        help='set one runtime parameter of a CONTRACT = 2 --env-plugin header (one of its PAR_NAMES; the others keep '
+             'the header\'s defaults); repeatable')
     return ap
 
 
@@ -107,6 +111,9 @@ def main(argv=None):
     argv = sys.argv[1:] if argv is None else argv
     torch.set_default_dtype(torch.float64)
     args = get_parser().parse_args(merge_argv(argv))
+    if args.env_param and args.env_plugin is None:  # refused here, before the save dir or the device is touched
+        from ._lib import PGMError
+        raise PGMError('--env-param sets a runtime parameter of an env plug-in: it needs --env-plugin HEADER')
     if args.env_plugin is not None or args.host_env == 'plugin':
         # every refusal of a plug-in run, before the save dir or the device is touched; then the env name is registered
         # with the header's dims and the loaded library travels in args.env_plugin
@@ -127,6 +134,14 @@ def main(argv=None):
             plugin.register(args.env_name)
         except ValueError as e:
             raise PGMError(f'--env-plugin with --env-name {args.env_name}: {e}') from e
+        env_params = {}
+        for item in args.env_param or ():
+            name, sep, value = str(item).partition('=')
+            if not sep or not name or not value:
+                raise PGMError(f'--env-param {item!r}: expected NAME=VALUE')
+            env_params[name] = value
+        plugin.par_vector(env_params)  # PGMError for an unknown name, a value that is no number, a header without any
+        args.env_params = {k: float(v) for k, v in env_params.items()}
         args.env_plugin = plugin
     elif args.host_env is not None and ':' in str(args.host_env):
         # an env name envspec does not know behind --host-env module:callable: a third-party env, registered with the

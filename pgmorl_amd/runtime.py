@@ -24,7 +24,9 @@ like SynthMO: the rollout is pgm_rollout_dummy, the evaluation pgm_eval_dummy, e
 
 With ``env_plugin`` (an ``envplug.EnvPlugin`` or the path of a user env header, include/pgm_envplug.h) the env is the
 user's own: the rollout is pgm_envplug_rollout and the evaluation pgm_envplug_eval of the plug-in's library, one launch
-each, and returns, advantages and the PPO update are the runtime-dim kernels of libpgm.so on the same storage.
+each, and returns, advantages and the PPO update are the runtime-dim kernels of libpgm.so on the same storage.  A
+contract-2 header (runtime parameters ``env_params``, per-step uniforms) goes through pgm_envplug_rollout_ex /
+pgm_envplug_eval_ex.
 """
 import ctypes as C
 import math
@@ -94,7 +96,7 @@ class TaskBatch:
                  clip_param=0.2, ppo_epoch=10, num_mini_batch=32, value_loss_coef=0.5, entropy_coef=0.0,
                  max_grad_norm=0.5, adam_eps=1e-5, use_clipped_value_loss=True, device='cuda', capacity=None,
                  layernorm=False, host_env=None, device_env=False, *, max_steps=None, time_limit_is_bad=None,
-                 bound=None, R=None, any_dims=False, env_plugin=None, run_seeds=None):
+                 bound=None, R=None, any_dims=False, env_plugin=None, run_seeds=None, env_params=None):
         """device_env: run a discrete-action env on the device (Deep Sea Treasure: pgm_rollout_dst / pgm_eval_dst)
         instead of on the host; for such an env exactly one of host_env and device_env=True is given.  The SynthMO envs
         are device envs already: the flag changes nothing there.  max_steps / time_limit_is_bad: the device Deep Sea
@@ -108,6 +110,10 @@ class TaskBatch:
         (envplug.EnvPlugin, or the path of its header): env_name is registered with the header's dims, the batch is a
         runtime-dim batch whose rollout and evaluation are the plug-in library's fused kernels, on the device envs'
         schedule (overlapped evaluation included); R: reset-table entries per env (default envplug.DEFAULT_RESETS).
+        env_params: the runtime parameters of a contract-2 plug-in, a dict name -> float over the header's PAR_NAMES
+        (omitted names take the header's default); one set for every task of the batch.  The plug-in's per-step
+        uniforms come from the stream of envplug.env_seed(rollout seed), the evaluation's from envplug.env_seed(seed):
+        fixed for the batch, so every policy it evaluates meets the same env noise.
         run_seeds: a list of seeds makes the batch hold the tasks of several runs (a sweep): the reset tables are
         stacked per run, task p resets from the block of run ``run_of_task[p]`` (set_runs) and env_reset / rollout /
         evaluate go through the *_runs entry points; `seed` is then unused.  SynthMO device envs only."""
@@ -141,10 +147,15 @@ class TaskBatch:
             if num_processes > 8:
                 raise PGMError(f'num_processes={num_processes} with env_plugin=...: envs per task > 8 unsupported')
             self.plugin = envplug.as_plugin(env_plugin)
+            self._plug_par_np = self.plugin.par_vector(env_params)  # (refuses unknown names, NP == 0)
+            self._plug_eval_seed = envplug.env_seed(seed)
             try:
                 self.plugin.register(env_name)
             except ValueError as e:
                 raise PGMError(f'env_plugin=...: {e}') from e
+        elif env_params:
+            raise PGMError('env_params=... sets the runtime parameters of env_plugin=...; this batch has no plug-in (a '
+                           'host-stepped plug-in takes them itself: hostenv.PluginHostVecEnv(..., env_params=...))')
         self.spec = envspec.make_spec(env_name)
         sp = self.spec
         self.host_env = host_env
@@ -288,6 +299,8 @@ class TaskBatch:
             self._plug_eval = torch.tensor(envspec.plugin_reset_table(seed, eval_num, self.R, pl.RW), dtype=F64,
                                            device=self.dev)
             self._plug_obs0 = torch.zeros(Pc, N, O, dtype=F64, device=self.dev)
+            self._plug_par = torch.tensor(self._plug_par_np if pl.NP else [0.0], dtype=F64, device=self.dev)
+            self.env_noise = None  # [T][N][NW] fp64, allocated by the first rollout that is fed its env noise
         # rollout storage (storage.py:12-30)
         z('obs', T + 1, N, O)
         z('actions', T, N, self.act_width)
@@ -420,12 +433,18 @@ class TaskBatch:
         check(lib().pgm_rollout_act(C.byref(self.dims), _ptr(self.params), C.byref(self.c_rb), t, _ptr(self.noise),
                                     _ptr(self._d_act), _stream()), 'pgm_rollout_act')
 
-    def _host_rollout(self, seed, noise, carry):
+    def _host_rollout(self, seed, noise, carry, env_noise=None):
         """morl/mopg.py:103-135 with the env on the host: per step t the device acts on obs[t], the actions go to the
         host (pinned D2H + the step's one stream synchronise), the host envs step, the transition returns (pinned
         H2D) and the device applies VecNormalize + insert into slot t + 1; then the bootstrap value."""
         import time
         P, T = self.P, self.T
+        if hasattr(self.host_env, 'begin_rollout'):  # a host-stepped contract-2 plug-in: this rollout's env noise
+            from . import envplug
+            self.host_env.begin_rollout(envplug.env_seed(seed), None if env_noise is None else
+                                        torch.as_tensor(env_noise).detach().cpu().numpy())
+        elif env_noise is not None:
+            raise PGMError('rollout(env_noise=...): only a contract-2 env plug-in with NW > 0 takes env noise')
         if noise is None:  # the perf-mode counter stream of `seed`: what the fused rollout draws in-kernel
             self._draw_noise(seed)
         elif noise is not self.noise:
@@ -647,7 +666,7 @@ class TaskBatch:
         if self.plugin is not None:  # env n of every task at entry (n, 0) of its row: the header's reset on the host
             P, N, pl = self.P, self.N, self.plugin
             row = np.broadcast_to(np.arange(N, dtype=np.int32), (P, N)).reshape(-1)
-            sd, si, obs = pl.reset(row, np.zeros(P * N, dtype=np.int32), self._plug_train_np)
+            sd, si, obs = pl.reset(row, np.zeros(P * N, dtype=np.int32), self._plug_train_np, par=self._plug_par_np)
             self.plug_sd.copy_(torch.from_numpy(sd.reshape(P, N, pl.SD)))
             self.plug_si.copy_(torch.from_numpy(si.reshape(P, N, pl.SI)))
             self._plug_obs0[:P].copy_(torch.from_numpy(obs.reshape(P, N, self.O)))
@@ -728,9 +747,13 @@ class TaskBatch:
                                     _ptr(value), _ptr(action), _ptr(logp), _stream()), 'pgm_act_forward')
         return value, action, logp
 
-    def rollout(self, seed, noise=None, carry=True):
+    def rollout(self, seed, noise=None, carry=True, env_noise=None):
+        """env_noise (a contract-2 plug-in with NW > 0, fused or host-stepped): the steps' uniforms [T][N][NW] in
+        [0, 1); None draws the stream of envplug.env_seed(seed)."""
         if self.host_env is not None:
-            return self._host_rollout(seed, noise, carry)
+            return self._host_rollout(seed, noise, carry, env_noise)
+        if env_noise is not None and (self.plugin is None or self.plugin.NW == 0):
+            raise PGMError('rollout(env_noise=...): only a contract-2 env plug-in with NW > 0 takes env noise')
         nz = None
         if noise is not None:
             if noise is not self.noise:
@@ -738,11 +761,31 @@ class TaskBatch:
             nz = self.noise
         if self.plugin is not None:  # noise: normals [T][N][A] / uniforms [T][N]; None: the counter stream of `seed`
             pl = self.plugin
-            pl.check(pl.h.pgm_envplug_rollout(C.byref(self.dims), _ptr(self.params), _ptr(self.plug_sd),
-                                              _ptr(self.plug_si), _ptr(self.episode), _ptr(self._plug_train), self.R,
-                                              self.N, C.byref(self.c_state), C.byref(self.c_norm), C.byref(self.c_rb),
-                                              _ptr(nz), C.c_uint64(seed), int(carry), _stream()),
-                     'pgm_envplug_rollout')
+            if pl.CONTRACT == 1:
+                pl.check(pl.h.pgm_envplug_rollout(C.byref(self.dims), _ptr(self.params), _ptr(self.plug_sd),
+                                                  _ptr(self.plug_si), _ptr(self.episode), _ptr(self._plug_train),
+                                                  self.R, self.N, C.byref(self.c_state), C.byref(self.c_norm),
+                                                  C.byref(self.c_rb), _ptr(nz), C.c_uint64(seed), int(carry),
+                                                  _stream()), 'pgm_envplug_rollout')
+                return
+            from . import envplug
+            ez = None
+            if env_noise is not None:
+                shape = (self.T, self.N, pl.NW)
+                if tuple(env_noise.shape) != shape:
+                    raise PGMError(f'rollout(env_noise=...) of shape {tuple(env_noise.shape)}: this batch steps '
+                                   f'[T][N][NW] = {shape}')
+                if self.env_noise is None:
+                    self.env_noise = torch.zeros(shape, dtype=F64, device=self.dev)
+                self.env_noise.copy_(torch.as_tensor(env_noise).to(dtype=F64))
+                ez = self.env_noise
+            pl.check(pl.h.pgm_envplug_rollout_ex(C.byref(self.dims), _ptr(self.params), _ptr(self.plug_sd),
+                                                 _ptr(self.plug_si), _ptr(self.episode), _ptr(self._plug_train),
+                                                 self.R, self.N, C.byref(self.c_state), C.byref(self.c_norm),
+                                                 C.byref(self.c_rb), _ptr(nz), C.c_uint64(seed), int(carry),
+                                                 _ptr(self._plug_par), _ptr(ez),
+                                                 C.c_uint64(envplug.env_seed(seed)), _stream()),
+                     'pgm_envplug_rollout_ex')
             return
         if self.device_env:  # noise: uniforms [T][N]; None: the kernel draws pgm_uniform_noise's stream of `seed`
             check(lib().pgm_rollout_dst(C.byref(self.dims), _ptr(self.params), C.byref(self.c_dst),
@@ -862,9 +905,17 @@ class TaskBatch:
             return self._host_evaluate(mean, var, out)
         if self.plugin is not None:
             pl = self.plugin
-            pl.check(pl.h.pgm_envplug_eval(C.byref(self.dims), _ptr(self.params), _ptr(self._plug_eval), self.R,
-                                           self.eval_num, _ptr(mean), _ptr(var), self.eval_num, int(self.use_ob_rms),
-                                           int(self.raw), self.gamma, _ptr(out), _stream()), 'pgm_envplug_eval')
+            if pl.CONTRACT == 1:
+                pl.check(pl.h.pgm_envplug_eval(C.byref(self.dims), _ptr(self.params), _ptr(self._plug_eval), self.R,
+                                               self.eval_num, _ptr(mean), _ptr(var), self.eval_num,
+                                               int(self.use_ob_rms), int(self.raw), self.gamma, _ptr(out), _stream()),
+                         'pgm_envplug_eval')
+                return out
+            pl.check(pl.h.pgm_envplug_eval_ex(C.byref(self.dims), _ptr(self.params), _ptr(self._plug_eval), self.R,
+                                              self.eval_num, _ptr(mean), _ptr(var), self.eval_num,
+                                              int(self.use_ob_rms), int(self.raw), self.gamma, _ptr(out),
+                                              _ptr(self._plug_par), C.c_uint64(self._plug_eval_seed), _stream()),
+                     'pgm_envplug_eval_ex')
             return out
         if self.device_env:
             check(lib().pgm_eval_dst(C.byref(self.dims), _ptr(self.params), C.byref(self.c_dst), _ptr(mean), _ptr(var),

@@ -628,6 +628,32 @@ int pgm_eval_episodes(const pgm_dims* d, const float* params, const pgm_env_spec
                       double gamma, int32_t stochastic, uint64_t noise_seed, double* episodes_out, double* objs_out,
                       pgm_stream_t stream);
 
+/* ---- Evaluation of policies blended between two members of a Pareto set (discovered by the presence of the symbol
+ * pgm_eval_blend; no feature bit, no version change).  Candidate q of d->P = Q candidates (d->N and d->T are not read)
+ * is (a, b) = src[q], alpha[q]: its parameter i is
+ *     (float)((1.0 - alpha) * (double)params[a][i] + alpha * (double)params[b][i])
+ * -- two fp64 products and one fp64 sum, each rounded on its own (no fma contraction), then one round to fp32 -- and its
+ * ob_mean / ob_var (use_ob_rms) the same expression in fp64 without the last round, so alpha = 0 is member a and
+ * alpha = 1 member b.  params [M][L], ob_mean / ob_var [M][O]: the M members, resident once; src int32 [Q][2] and alpha
+ * fp64 [Q] are DEVICE memory and are not read on the host.  The blend is formed in the kernel's weight load: no
+ * candidate is materialised.  evaluation() (morl/mopg.py:25-46) of each candidate, deterministic policy, from each of
+ * the E start states starts [E][O], on the SynthMO device envs.  One wave per (candidate, episode) with pgm_eval's wave
+ * kernel body: work item w = q * E + e, 4 waves per 256-thread workgroup, grid ceil(Q * E / 4); no LDS and no
+ * workgroup barrier.  A candidate whose src entry lies outside [0, M) reads no parameters and gets NaN in its K sums
+ * of every episode.
+ * episodes_out [Q][E][K] fp64: each episode's sum of g * obj, g = gamma^t unless raw.  objs_out [Q][K] (may be NULL):
+ * the episode sums added in index order, divided by E (the kernel pgm_eval_episodes uses).
+ * Plain towers at the dims of the wave kernel only (obs_dim <= 48, K <= 4: every SynthMO dim set but 376/17/2): for
+ * LayerNorm towers and MO-Humanoid the caller materialises the candidates and uses pgm_eval_episodes.
+ * Validation, before any device work, in this order: NULL pointers (d, params, src, alpha, spec, starts, episodes_out;
+ * ob_mean / ob_var with use_ob_rms) PGM_E_INVALID_ARG; the dims with N = 1, T = 0 as pgm_eval_act checks them;
+ * pgm_dims.LN, then LN = 1 PGM_E_UNSUPPORTED; a NULL field of spec or max_episode_steps <= 0 PGM_E_INVALID_ARG; M >= 1,
+ * 1 <= E <= 65536 and Q * E <= 2^24 else PGM_E_SHAPE; then a dim set outside the wave kernel PGM_E_UNSUPPORTED. */
+int pgm_eval_blend(const pgm_dims* d, const float* params, int32_t M, const double* ob_mean, const double* ob_var,
+                   const int32_t* src, const double* alpha, const pgm_env_spec* spec, const double* starts, int32_t E,
+                   int32_t use_ob_rms, int32_t raw, double gamma, double* episodes_out, double* objs_out,
+                   pgm_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -178,10 +178,15 @@ _SIGS = {
     # ob_var, starts, E, use_ob_rms, raw, gamma, stochastic, noise_seed, episodes_out, objs_out
     'pgm_eval_episodes': (C.c_int, [C.POINTER(Dims), P_, C.POINTER(EnvSpec), P_, P_, P_, I32, I32, I32, F64, I32,
                                     C.c_uint64, P_, P_, P_]),
+    # a dense front from blended members (no feature bit: discovered by the symbol itself): params, M, ob_mean, ob_var,
+    # src, alpha, spec, starts, E, use_ob_rms, raw, gamma, episodes_out, objs_out
+    'pgm_eval_blend': (C.c_int, [C.POINTER(Dims), P_, I32, P_, P_, P_, P_, C.POINTER(EnvSpec), P_, I32, I32, I32, F64,
+                                 P_, P_, P_]),
 }
 RUNS_SYMBOLS = ('pgm_env_reset_runs', 'pgm_rollout_runs', 'pgm_eval_runs')
 TASKS_SYMBOLS = ('pgm_ppo_update_tasks', 'pgm_gae_tasks')
 EVAL_EPISODES_SYMBOLS = ('pgm_eval_episodes',)
+EVAL_BLEND_SYMBOLS = ('pgm_eval_blend',)
 EVAL_EPISODES_MAX = 65536  # episodes per policy in one pgm_eval_episodes call
 TASK_HPARAM_FIELDS =('clip_param', 'value_loss_coef', 'entropy_coef', 'max_grad_norm')  # pgm_task_hparams, in order
 # the symbols a library of the same ABI version and minor may lack: discovered through pgm_abi_features
@@ -219,9 +224,9 @@ def _load(path):
         h = C.CDLL(path)
         for name, (res, args) in _SIGS.items():
             if (name in _FEATURE_SYMBOLS or name in RUNS_SYMBOLS or name in TASKS_SYMBOLS or
-                    name in EVAL_EPISODES_SYMBOLS) and not hasattr(h, name):
+                    name in EVAL_EPISODES_SYMBOLS or name in EVAL_BLEND_SYMBOLS) and not hasattr(h, name):
                 continue  # an older library of this ABI: features() / has_runs() / has_tasks() / has_eval_episodes()
-                # report what is missing
+                # / has_eval_blend() report what is missing
             f = getattr(h, name)
             f.restype, f.argtypes = res, args
         if h.pgm_abi_version() != PGM_ABI_VERSION:
@@ -328,6 +333,18 @@ def has_eval_episodes():
 def require_eval_episodes():
     if not has_eval_episodes():
         raise PGMError('this libpgm.so has no pgm_eval_episodes (the re-evaluation of a saved Pareto set); '
+                       'rebuild it with `python -m pgmorl_amd.build`')
+
+
+def has_eval_blend():
+    """True if the library has pgm_eval_blend (evaluation of policies blended between two members of a Pareto set):
+    the presence of the symbol, as include/pgm_abi.h documents (there is no feature bit)."""
+    return hasattr(lib(), 'pgm_eval_blend')
+
+
+def require_eval_blend():
+    if not has_eval_blend():
+        raise PGMError('this libpgm.so has no pgm_eval_blend (the evaluation of blended policies); '
                        'rebuild it with `python -m pgmorl_amd.build`')
 
 

@@ -225,6 +225,26 @@ using RolloutArgsT = std::conditional_t<RUNS, RolloutRunsArgs, RolloutArgs>;
 template <bool RUNS>
 using EvalArgsT = std::conditional_t<RUNS, EvalRunsArgs, EvalArgs>;
 
+// pgm_eval_blend: candidate q is the blend (src[q][0], src[q][1], alpha[q]) of two of the M member policies
+struct EvalBlendArgs {
+    int Q, E, M;
+    Layout L;
+    const float* params;  // [M][L]
+    pgm_env_spec spec;
+    const double *ob_mean, *ob_var;  // [M][O]; read with use_ob
+    const double* starts;            // [E][O]
+    const int32_t* src;              // [Q][2], device
+    const double* alpha;             // [Q], device
+    int use_ob, raw;
+    double gamma;
+    double* episodes;  // [Q][E][K]
+};
+constexpr int EVAL_BLEND_WAVES = 4;           // waves per workgroup, one (candidate, episode) each
+constexpr int EVAL_BLEND_WORK_MAX = 1 << 24;  // (candidate, episode) waves of one call
+// blended-policy evaluation (pgm_rollout_lanes.hip): plain towers at the dims of eval_waves_supported;
+// PGM_E_UNSUPPORTED without launching outside them
+int launch_eval_blend(const pgm_dims* d, const EvalBlendArgs& a, hipStream_t stream);
+
 // Lane-parallel kernels (pgm_rollout_lanes.hip).  Each returns PGM_E_UNSUPPORTED without launching when
 // the dims are outside its envelope (the caller then uses the block-per-task kernel).
 // (runs != nullptr: the RUNS instantiation with that run_of_task)

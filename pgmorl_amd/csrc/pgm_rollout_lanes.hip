@@ -182,20 +182,25 @@ struct ActorLane {
     float w1[O], w2[H], wm[A], bm[A], ls[A], sd[A], rsd[A];
     float b1, b2;
     __device__ void load(const float* __restrict__ prm, const Layout& L, int l) {
+        load_from([prm](int i) { return prm[i]; }, L, l);
+    }
+    // rd(i): element i of the policy's flat parameter row (eval_blend_kernel reads a blend of two rows)
+    template <class F>
+    __device__ void load_from(F rd, const Layout& L, int l) {
 #pragma unroll
-        for (int k = 0; k < O; ++k) w1[k] = prm[L.off[PGM_P_ACTOR_W1] + k * H + l];
+        for (int k = 0; k < O; ++k) w1[k] = rd(L.off[PGM_P_ACTOR_W1] + k * H + l);
 #pragma unroll
-        for (int k = 0; k < H; ++k) w2[k] = prm[L.off[PGM_P_ACTOR_W2] + k * H + l];
+        for (int k = 0; k < H; ++k) w2[k] = rd(L.off[PGM_P_ACTOR_W2] + k * H + l);
 #pragma unroll
         for (int j = 0; j < A; ++j) {
-            wm[j] = prm[L.off[PGM_P_MEAN_W] + l * A + j];
-            bm[j] = prm[L.off[PGM_P_MEAN_B] + j];
-            ls[j] = prm[L.off[PGM_P_LOGSTD] + j];
+            wm[j] = rd(L.off[PGM_P_MEAN_W] + l * A + j);
+            bm[j] = rd(L.off[PGM_P_MEAN_B] + j);
+            ls[j] = rd(L.off[PGM_P_LOGSTD] + j);
             sd[j] = expf(ls[j]);
             rsd[j] = 1.0f / sd[j];
         }
-        b1 = prm[L.off[PGM_P_ACTOR_B1] + l];
-        b2 = prm[L.off[PGM_P_ACTOR_B2] + l];
+        b1 = rd(L.off[PGM_P_ACTOR_B1] + l);
+        b2 = rd(L.off[PGM_P_ACTOR_B2] + l);
         // the per-action constants are wave-uniform; kept in VGPRs (the SGPR file is the step loop's scarce
         // resource: spilled SGPRs come back through v_readlane + s_nop every step)
 #pragma unroll
@@ -1058,6 +1063,73 @@ __global__ __launch_bounds__(64 * EVAL_MAX_WAVES) void eval_wave_kernel(EvalArgs
     }
 }
 
+// ------------------------------------------------------------------------------------------ blended evaluation
+// (1 - alpha) x + alpha y as two fp64 products and one fp64 sum, each rounded on its own: what numpy computes for
+// (1 - alpha) * x + alpha * y, so alpha = 0 gives x and alpha = 1 gives y (w0 = 1 - alpha)
+__device__ __forceinline__ double blend_d(double w0, double alpha, double x, double y) {
+#pragma clang fp contract(off)
+    const double px = w0 * x;
+    const double py = alpha * y;
+    return px + py;
+}
+
+// pgm_eval_blend: one wave per (candidate, episode), work item w = q * E + e on wave w % EVAL_BLEND_WAVES of
+// workgroup w / EVAL_BLEND_WAVES.  The body is eval_wave_kernel's with the policy's weights and observation statistics
+// read through the blend; no LDS, no workgroup barrier, each wave stores its own K sums.  Two waves per SIMD, the
+// register budget of eval_wave_kernel: a wave is one dependent chain, so a second wave fills its issue gaps.
+template <int O, int A, int K>
+__global__ __launch_bounds__(64 * EVAL_BLEND_WAVES, 2) void eval_blend_kernel(EvalBlendArgs a) {
+    const int l = threadIdx.x & 63;
+    const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const size_t w = (size_t)blockIdx.x * EVAL_BLEND_WAVES + wv;
+    if (w >= (size_t)a.Q * a.E) return;  // the last workgroup's spare waves (wave-uniform; nothing waits for them)
+    const int q = (int)(w / a.E), e = (int)(w % a.E);
+    const int ia = a.src[2 * q], ib = a.src[2 * q + 1];
+    double* out = a.episodes + w * K;
+    if (ia < 0 || ia >= a.M || ib < 0 || ib >= a.M) {  // a member that does not exist: nothing of it is read
+        if (l < K) out[l] = __builtin_nan("");
+        return;
+    }
+    const double al = a.alpha[q], w0 = 1.0 - al;
+    const float* pa = a.params + (size_t)ia * a.L.total;
+    const float* pb = a.params + (size_t)ib * a.L.total;
+    ActorLane<O, A> pol;
+    pol.load_from([=](int i) { return (float)blend_d(w0, al, (double)pa[i], (double)pb[i]); }, a.L, l);
+    EnvLane<O, A, K> env;
+    env.load(a.spec, l);
+    const int lo = l < O ? l : 0;
+    // each member carries its own frozen normaliser: the candidate's is the same blend, in fp64
+    double mean = 0.0, inv = 1.0;
+    if (a.use_ob) {
+        mean = blend_d(w0, al, a.ob_mean[(size_t)ia * O + lo], a.ob_mean[(size_t)ib * O + lo]);
+        inv = 1.0 / sqrt(blend_d(w0, al, a.ob_var[(size_t)ia * O + lo], a.ob_var[(size_t)ib * O + lo]) + 1e-8);
+    }
+    const int maxs = a.spec.max_episode_steps;
+    double s = a.starts[(size_t)e * O + lo];
+    double acc[K], g = 1.0;
+#pragma unroll
+    for (int k = 0; k < K; ++k) acc[k] = 0.0;
+    for (int st = 0; st < maxs; ++st) {  // eval_wave_kernel's step, statement by statement
+        float mu[A];
+        double v = s;
+        if (a.use_ob) v = clipd((v - mean) * inv, -10.0, 10.0);
+        pol.forward_reg((float)v, mu);
+        double ac[A], sq[A];
+#pragma unroll
+        for (int j = 0; j < A; ++j) {
+            ac[j] = clipd((double)mu[j], env.lo[j], env.hi[j]);
+            sq[j] = ac[j] * ac[j];
+        }
+        const double e2 = tree_sum(sq);
+        double objraw[K];
+        s = env.step(s, ac, e2, objraw);
+#pragma unroll
+        for (int k = 0; k < K; ++k) acc[k] += g * objraw[k];
+        if (!a.raw) g *= a.gamma;
+    }
+    if (l < K) out[l] = sel_lane_d(acc, l);
+}
+
 // ------------------------------------------------------------------------------------------ launchers
 template <class Kern, class Args>
 static int launch_k(Kern k, dim3 grid, dim3 block, size_t smem, hipStream_t s, const Args& args, const char* what) {
@@ -1144,6 +1216,22 @@ int launch_eval_waves(const pgm_dims* d, const EvalArgs& a, hipStream_t stream, 
                                 EvalRunsArgs{a, runs}, "pgm_eval");
             return launch_k(eval_wave_kernel<O, A, K, false>, dim3(d->P), dim3(64 * nw), sizeof(EvalSmem<O>), stream, a,
                             "pgm_eval");
+        }
+    });
+}
+
+int launch_eval_blend(const pgm_dims* d, const EvalBlendArgs& a, hipStream_t stream) {
+    return dispatch_dims(d->O, d->A, d->K, "pgm_eval_blend", [&](auto o, auto aa, auto k) -> int {
+        constexpr int O = decltype(o)::value, A = decltype(aa)::value, K = decltype(k)::value;
+        if constexpr (!lanes_fit<O, K>() || K > 4) {
+            set_error("pgm_eval_blend: dims %d/%d/%d are outside the wave-per-episode kernel; materialise the candidates "
+                      "and use pgm_eval_episodes", O, A, K);
+            return PGM_E_UNSUPPORTED;
+        } else {
+            const size_t work = (size_t)a.Q * a.E;
+            const unsigned grid = (unsigned)((work + EVAL_BLEND_WAVES - 1) / EVAL_BLEND_WAVES);
+            hipLaunchKernelGGL((eval_blend_kernel<O, A, K>), dim3(grid), dim3(64 * EVAL_BLEND_WAVES), 0, stream, a);
+            return launch_status("pgm_eval_blend");
         }
     });
 }

@@ -654,6 +654,24 @@ int pgm_eval_blend(const pgm_dims* d, const float* params, int32_t M, const doub
                    int32_t use_ob_rms, int32_t raw, double gamma, double* episodes_out, double* objs_out,
                    pgm_stream_t stream);
 
+/* ---- Evaluation of policies blended among three members of a Pareto set: the simplex candidates of a three-objective
+ * front (discovered by the presence of the symbol pgm_eval_blend3; no feature bit, no version change).  Candidate q of
+ * d->P = Q candidates is (a, b, c) = src[q], (wa, wb, wc) = w[q]: its parameter i is
+ *     (float)((wa * (double)params[a][i] + wb * (double)params[b][i]) + wc * (double)params[c][i])
+ * -- three fp64 products and two fp64 sums, left to right, each rounded on its own (no fma contraction), then one round
+ * to fp32 -- and its ob_mean / ob_var (use_ob_rms) the same expression in fp64 without the last round.  So
+ * (i, i, i, 1, 0, 0) is member i, (a, b, b, 1 - alpha, alpha, 0) has the value of pgm_eval_blend's (a, b, alpha), and
+ * swapping the first two (index, weight) slots changes no bit.  src int32 [Q][3] and w fp64 [Q][3] are DEVICE memory
+ * and are not read on the host; the caller keeps the weights in [0, 1] with sum 1.  Everything else -- the members,
+ * the start states, the kernel form (one wave per (candidate, episode), work item w = q * E + e, 4 waves per
+ * 256-thread workgroup, no LDS, no workgroup barrier), the NaN of a candidate whose src names a member outside
+ * [0, M), episodes_out [Q][E][K], objs_out [Q][K] (may be NULL), the dims covered and the validation order with its
+ * limits -- is pgm_eval_blend's, with w in the place of alpha; every message starts with "pgm_eval_blend3:". */
+int pgm_eval_blend3(const pgm_dims* d, const float* params, int32_t M, const double* ob_mean, const double* ob_var,
+                    const int32_t* src, const double* w, const pgm_env_spec* spec, const double* starts, int32_t E,
+                    int32_t use_ob_rms, int32_t raw, double gamma, double* episodes_out, double* objs_out,
+                    pgm_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -182,11 +182,16 @@ _SIGS = {
     # src, alpha, spec, starts, E, use_ob_rms, raw, gamma, episodes_out, objs_out
     'pgm_eval_blend': (C.c_int, [C.POINTER(Dims), P_, I32, P_, P_, P_, P_, C.POINTER(EnvSpec), P_, I32, I32, I32, F64,
                                  P_, P_, P_]),
+    # simplex candidates of a three-objective front (no feature bit: discovered by the symbol itself): pgm_eval_blend's
+    # arguments with src int32 [Q][3] and w fp64 [Q][3] in the places of src and alpha
+    'pgm_eval_blend3': (C.c_int, [C.POINTER(Dims), P_, I32, P_, P_, P_, P_, C.POINTER(EnvSpec), P_, I32, I32, I32, F64,
+                                  P_, P_, P_]),
 }
 RUNS_SYMBOLS = ('pgm_env_reset_runs', 'pgm_rollout_runs', 'pgm_eval_runs')
 TASKS_SYMBOLS = ('pgm_ppo_update_tasks', 'pgm_gae_tasks')
 EVAL_EPISODES_SYMBOLS = ('pgm_eval_episodes',)
 EVAL_BLEND_SYMBOLS = ('pgm_eval_blend',)
+EVAL_BLEND3_SYMBOLS = ('pgm_eval_blend3',)
 EVAL_EPISODES_MAX = 65536  # episodes per policy in one pgm_eval_episodes call
 TASK_HPARAM_FIELDS =('clip_param', 'value_loss_coef', 'entropy_coef', 'max_grad_norm')  # pgm_task_hparams, in order
 # the symbols a library of the same ABI version and minor may lack: discovered through pgm_abi_features
@@ -224,9 +229,10 @@ def _load(path):
         h = C.CDLL(path)
         for name, (res, args) in _SIGS.items():
             if (name in _FEATURE_SYMBOLS or name in RUNS_SYMBOLS or name in TASKS_SYMBOLS or
-                    name in EVAL_EPISODES_SYMBOLS or name in EVAL_BLEND_SYMBOLS) and not hasattr(h, name):
+                    name in EVAL_EPISODES_SYMBOLS or name in EVAL_BLEND_SYMBOLS or
+                    name in EVAL_BLEND3_SYMBOLS) and not hasattr(h, name):
                 continue  # an older library of this ABI: features() / has_runs() / has_tasks() / has_eval_episodes()
-                # / has_eval_blend() report what is missing
+                # / has_eval_blend() / has_eval_blend3() report what is missing
             f = getattr(h, name)
             f.restype, f.argtypes = res, args
         if h.pgm_abi_version() != PGM_ABI_VERSION:
@@ -345,6 +351,18 @@ def has_eval_blend():
 def require_eval_blend():
     if not has_eval_blend():
         raise PGMError('this libpgm.so has no pgm_eval_blend (the evaluation of blended policies); '
+                       'rebuild it with `python -m pgmorl_amd.build`')
+
+
+def has_eval_blend3():
+    """True if the library has pgm_eval_blend3 (evaluation of policies blended among three members of a Pareto set):
+    the presence of the symbol, as include/pgm_abi.h documents (there is no feature bit)."""
+    return hasattr(lib(), 'pgm_eval_blend3')
+
+
+def require_eval_blend3():
+    if not has_eval_blend3():
+        raise PGMError('this libpgm.so has no pgm_eval_blend3 (the evaluation of three-member blends); '
                        'rebuild it with `python -m pgmorl_amd.build`')
 
 

@@ -189,4 +189,53 @@ int pgm_eval_blend(const pgm_dims* d, const float* params, int32_t M, const doub
                        objs_out, d->P, E, d->K);
     return launch_status(what);
 }
+
+// Validation order (include/pgm_abi.h): pgm_eval_blend's, item by item; then the dispatch refuses dims outside the
+// wave-per-episode kernel (eval_blend3_kernel, pgm_rollout_lanes.hip).
+int pgm_eval_blend3(const pgm_dims* d, const float* params, int32_t M, const double* ob_mean, const double* ob_var,
+                    const int32_t* src, const double* w, const pgm_env_spec* spec, const double* starts, int32_t E,
+                    int32_t use_ob_rms, int32_t raw, double gamma, double* episodes_out, double* objs_out,
+                    pgm_stream_t stream) {
+    const char* what = "pgm_eval_blend3";
+    if (!d || !params || !src || !w || !spec || !starts || !episodes_out || (use_ob_rms && (!ob_mean || !ob_var))) {
+        set_error("%s: null pointer (ob_mean / ob_var are required with use_ob_rms; objs_out may be NULL)", what);
+        return PGM_E_INVALID_ARG;
+    }
+    pgm_dims dd = *d;  // N and T are not this call's: P = Q candidates, a wave per (candidate, episode)
+    dd.N = 1;
+    dd.T = 0;
+    if (int rc = check_dims(&dd, what)) return rc;
+    if (int rc = check_ln(&dd, what)) return rc;
+    if (dd.LN == 1) {
+        set_error("%s: LayerNorm towers (pgm_dims.LN = 1) have no wave-per-episode kernel; materialise the candidates "
+                  "and use pgm_eval_episodes", what);
+        return PGM_E_UNSUPPORTED;
+    }
+    if (!spec_ok(spec)) {
+        set_error("%s: null pointer in the env spec, or max_episode_steps <= 0", what);
+        return PGM_E_INVALID_ARG;
+    }
+    if (M < 1) {
+        set_error("%s: M=%d members outside [1, 2^31)", what, M);
+        return PGM_E_SHAPE;
+    }
+    if (E < 1 || E > EVAL_EPISODES_MAX) {
+        set_error("%s: E=%d episodes per candidate outside [1, %d]", what, E, EVAL_EPISODES_MAX);
+        return PGM_E_SHAPE;
+    }
+    if ((int64_t)d->P * E > EVAL_BLEND_WORK_MAX) {
+        set_error("%s: Q * E = %d * %d exceeds the %d (candidate, episode) waves of one call; send the table in slices",
+                  what, d->P, E, EVAL_BLEND_WORK_MAX);
+        return PGM_E_SHAPE;
+    }
+    const EvalBlend3Args a{d->P, E, M, make_layout(d->O, d->A, d->K, d->H), params, *spec, ob_mean, ob_var, starts, src,
+                           w, use_ob_rms != 0, raw != 0, gamma, episodes_out};
+    const hipStream_t s = (hipStream_t)stream;
+    const int rc = launch_eval_blend3(&dd, a, s);
+    if (rc != PGM_OK || !objs_out) return rc;
+    const size_t n = (size_t)d->P * d->K;
+    hipLaunchKernelGGL(eval_episodes_mean_kernel, dim3((unsigned)((n + RT - 1) / RT)), dim3(RT), 0, s, episodes_out,
+                       objs_out, d->P, E, d->K);
+    return launch_status(what);
+}
 }  // extern "C"

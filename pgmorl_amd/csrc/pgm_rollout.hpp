@@ -245,6 +245,23 @@ constexpr int EVAL_BLEND_WORK_MAX = 1 << 24;  // (candidate, episode) waves of o
 // PGM_E_UNSUPPORTED without launching outside them
 int launch_eval_blend(const pgm_dims* d, const EvalBlendArgs& a, hipStream_t stream);
 
+// pgm_eval_blend3: candidate q is the simplex blend (src[q][0..2], w[q][0..2]) of three of the M member policies
+struct EvalBlend3Args {
+    int Q, E, M;
+    Layout L;
+    const float* params;  // [M][L]
+    pgm_env_spec spec;
+    const double *ob_mean, *ob_var;  // [M][O]; read with use_ob
+    const double* starts;            // [E][O]
+    const int32_t* src;              // [Q][3], device
+    const double* w;                 // [Q][3], device
+    int use_ob, raw;
+    double gamma;
+    double* episodes;  // [Q][E][K]
+};
+// three-member blended evaluation (pgm_rollout_lanes.hip): launch_eval_blend's dims, work flattening and limits
+int launch_eval_blend3(const pgm_dims* d, const EvalBlend3Args& a, hipStream_t stream);
+
 // Lane-parallel kernels (pgm_rollout_lanes.hip).  Each returns PGM_E_UNSUPPORTED without launching when
 // the dims are outside its envelope (the caller then uses the block-per-task kernel).
 // (runs != nullptr: the RUNS instantiation with that run_of_task)

@@ -1130,6 +1130,76 @@ __global__ __launch_bounds__(64 * EVAL_BLEND_WAVES, 2) void eval_blend_kernel(Ev
     if (l < K) out[l] = sel_lane_d(acc, l);
 }
 
+// (wa x + wb y) + wc z as three fp64 products and two fp64 sums, left to right, each rounded on its own: numpy's
+// (wa * x + wb * y) + wc * z.  Formed source by source, so one row's value is consumed before the next is needed.
+__device__ __forceinline__ double blend3_d(double wa, double wb, double wc, double x, double y, double z) {
+#pragma clang fp contract(off)
+    double t = wa * x;
+    const double py = wb * y;
+    t = t + py;
+    const double pz = wc * z;
+    t = t + pz;
+    return t;
+}
+
+// pgm_eval_blend3: eval_blend_kernel with three source rows per candidate (src [Q][3], w [Q][3]); the same work
+// flattening, budget and step loop, the latter restated statement by statement.
+template <int O, int A, int K>
+__global__ __launch_bounds__(64 * EVAL_BLEND_WAVES, 2) void eval_blend3_kernel(EvalBlend3Args a) {
+    const int l = threadIdx.x & 63;
+    const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const size_t w = (size_t)blockIdx.x * EVAL_BLEND_WAVES + wv;
+    if (w >= (size_t)a.Q * a.E) return;  // the last workgroup's spare waves (wave-uniform; nothing waits for them)
+    const int q = (int)(w / a.E), e = (int)(w % a.E);
+    const int ia = a.src[3 * q], ib = a.src[3 * q + 1], ic = a.src[3 * q + 2];
+    double* out = a.episodes + w * K;
+    if (ia < 0 || ia >= a.M || ib < 0 || ib >= a.M || ic < 0 || ic >= a.M) {  // nothing of such a member is read
+        if (l < K) out[l] = __builtin_nan("");
+        return;
+    }
+    const double wa = a.w[3 * q], wb = a.w[3 * q + 1], wc = a.w[3 * q + 2];
+    const float* pa = a.params + (size_t)ia * a.L.total;
+    const float* pb = a.params + (size_t)ib * a.L.total;
+    const float* pc = a.params + (size_t)ic * a.L.total;
+    ActorLane<O, A> pol;
+    pol.load_from([=](int i) { return (float)blend3_d(wa, wb, wc, (double)pa[i], (double)pb[i], (double)pc[i]); },
+                  a.L, l);
+    EnvLane<O, A, K> env;
+    env.load(a.spec, l);
+    const int lo = l < O ? l : 0;
+    // the candidate's frozen normaliser is the same three-way blend of the members', in fp64
+    double mean = 0.0, inv = 1.0;
+    if (a.use_ob) {
+        const size_t oa = (size_t)ia * O + lo, ob = (size_t)ib * O + lo, oc = (size_t)ic * O + lo;
+        mean = blend3_d(wa, wb, wc, a.ob_mean[oa], a.ob_mean[ob], a.ob_mean[oc]);
+        inv = 1.0 / sqrt(blend3_d(wa, wb, wc, a.ob_var[oa], a.ob_var[ob], a.ob_var[oc]) + 1e-8);
+    }
+    const int maxs = a.spec.max_episode_steps;
+    double s = a.starts[(size_t)e * O + lo];
+    double acc[K], g = 1.0;
+#pragma unroll
+    for (int k = 0; k < K; ++k) acc[k] = 0.0;
+    for (int st = 0; st < maxs; ++st) {  // eval_wave_kernel's step, statement by statement
+        float mu[A];
+        double v = s;
+        if (a.use_ob) v = clipd((v - mean) * inv, -10.0, 10.0);
+        pol.forward_reg((float)v, mu);
+        double ac[A], sq[A];
+#pragma unroll
+        for (int j = 0; j < A; ++j) {
+            ac[j] = clipd((double)mu[j], env.lo[j], env.hi[j]);
+            sq[j] = ac[j] * ac[j];
+        }
+        const double e2 = tree_sum(sq);
+        double objraw[K];
+        s = env.step(s, ac, e2, objraw);
+#pragma unroll
+        for (int k = 0; k < K; ++k) acc[k] += g * objraw[k];
+        if (!a.raw) g *= a.gamma;
+    }
+    if (l < K) out[l] = sel_lane_d(acc, l);
+}
+
 // ------------------------------------------------------------------------------------------ launchers
 template <class Kern, class Args>
 static int launch_k(Kern k, dim3 grid, dim3 block, size_t smem, hipStream_t s, const Args& args, const char* what) {
@@ -1232,6 +1302,22 @@ int launch_eval_blend(const pgm_dims* d, const EvalBlendArgs& a, hipStream_t str
             const unsigned grid = (unsigned)((work + EVAL_BLEND_WAVES - 1) / EVAL_BLEND_WAVES);
             hipLaunchKernelGGL((eval_blend_kernel<O, A, K>), dim3(grid), dim3(64 * EVAL_BLEND_WAVES), 0, stream, a);
             return launch_status("pgm_eval_blend");
+        }
+    });
+}
+
+int launch_eval_blend3(const pgm_dims* d, const EvalBlend3Args& a, hipStream_t stream) {
+    return dispatch_dims(d->O, d->A, d->K, "pgm_eval_blend3", [&](auto o, auto aa, auto k) -> int {
+        constexpr int O = decltype(o)::value, A = decltype(aa)::value, K = decltype(k)::value;
+        if constexpr (!lanes_fit<O, K>() || K > 4) {
+            set_error("pgm_eval_blend3: dims %d/%d/%d are outside the wave-per-episode kernel; materialise the "
+                      "candidates and use pgm_eval_episodes", O, A, K);
+            return PGM_E_UNSUPPORTED;
+        } else {
+            const size_t work = (size_t)a.Q * a.E;
+            const unsigned grid = (unsigned)((work + EVAL_BLEND_WAVES - 1) / EVAL_BLEND_WAVES);
+            hipLaunchKernelGGL((eval_blend3_kernel<O, A, K>), dim3(grid), dim3(64 * EVAL_BLEND_WAVES), 0, stream, a);
+            return launch_status("pgm_eval_blend3");
         }
     });
 }

@@ -1057,6 +1057,12 @@ int ppo_update_wide(const pgm_dims* d, const pgm_ppo_hparams* hp, float* params,
                   "((T+1) N O = %lld floats)", (long long)(d->T + 1) * d->N * d->O);
         return PGM_E_UNSUPPORTED;
     }
+    // every workgroup's layer-1 copy [P][2 towers][ns parts][O H] (filled by the kernel) in the workspace's copy region,
+    // sized for PGM_NS_MAX parts (ppo_workspace_bytes); refused before the workspace's zeroed mark is consumed
+    if (ns > PGM_NS_MAX) {
+        set_error("pgm_ppo_update: wide layer-1 copies exceed the workspace (ns=%d)", ns);
+        return PGM_E_INVALID_ARG;
+    }
     const Layout L = make_layout(d->O, d->A, d->K, d->H);
     char* ws = (char*)workspace;
     const size_t flags = ppo_flag_bytes(d->P);
@@ -1071,12 +1077,6 @@ int ppo_update_wide(const pgm_dims* d, const pgm_ppo_hparams* hp, float* params,
     if (!ws_take_zeroed(workspace, flags + (ns > 1 ? xbytes : 0))) {
         e = hipMemsetAsync(workspace, 0, flags + (ns > 1 ? xbytes : 0), stream);
         if (e != hipSuccess) return hip_fail(e, "pgm_ppo_update (workspace reset)");
-    }
-    // every workgroup's layer-1 copy [P][2 towers][ns parts][O H] (filled by the kernel) in the workspace's copy region,
-    // sized for PGM_NS_MAX parts (ppo_workspace_bytes)
-    if (ns > PGM_NS_MAX) {
-        set_error("pgm_ppo_update: wide layer-1 copies exceed the workspace (ns=%d)", ns);
-        return PGM_E_INVALID_ARG;
     }
     return dispatch_dims(d->O, d->A, d->K, "pgm_ppo_update", [&](auto o, auto aa, auto k) -> int {
         constexpr int O = decltype(o)::value, A = decltype(aa)::value, K = decltype(k)::value;

@@ -33,7 +33,7 @@ pytestmark = pytest.mark.gpu
 # kernel -> (its uniform-table case of branch_inputs.oracle_case, its mixed cases of grid_inputs)
 CASES = {k: (('hopper2', False), ('hopper',)) for k in ('fs', 'mfma4', 'mfma2', 'mfma1', 'mfma0', 'valu')}
 CASES['fs'] = (('hopper2', False), ('hopper', 'walker'))
-CASES['wide'] = (('humanoid32', False), ('humanoid',))
+CASES['wide'] = CASES['wide1'] = CASES['wide2'] = (('humanoid32', False), ('humanoid',))
 CASES['ln'] = (('hopper2', True), ('hopper_ln',))
 MIXED = [(k, c) for k, (_, cs) in CASES.items() for c in cs]
 ARRAYS = ('params', 'adam_m', 'adam_v', 'adam_step', 'stats')

@@ -146,9 +146,10 @@ def test_adv_normalize(gpu, use_obj_rms):
         _close(got[p], ref.numpy(), 1e-5, 1e-5, 'advantages')
 
 
-def _update_setup(env, P, T, N, E, M, seed, **kw):
-    args = small_args(env, num_steps=T, num_processes=N, ppo_epoch=E, num_mini_batch=M)
-    spec, tb, pols = _batch_with_policies(env, P, N, T, seed=seed, scale=0.05, ppo_epoch=E, num_mini_batch=M, **kw)
+def _update_data(spec, pols, T, N, E, seed):
+    """Rollout storage for one update of every policy, from its own fp64 forward -> ((obs, actions, logp, values,
+    returns, adv) as fp32 arrays shaped like the TaskBatch buffers, one permutation per epoch)."""
+    P = len(pols)
     O, A, K, B = spec['obs_dim'], spec['act_dim'], spec['obj_num'], T * N
     rng = np.random.RandomState(seed)
     obs = np.clip(rng.randn(P, T + 1, N, O), -3, 3).astype(np.float32)
@@ -165,11 +166,23 @@ def _update_setup(env, P, T, N, E, M, seed, **kw):
     values = torch.cat([values, torch.zeros(P, 1, N, K)], 1)
     returns = (values + torch.from_numpy(rng.randn(P, T + 1, N, K) * 0.5).float())
     adv = torch.from_numpy(rng.randn(P, T, N)).float()
+    perms = [torch.randperm(B, generator=torch.Generator().manual_seed(seed * 10 + e)) for e in range(E)]
+    return (obs, actions, logp, values, returns, adv), perms
+
+
+def _load_update_data(tb, data):
+    obs, actions, logp, values, returns, adv = data
     for dst, src in ((tb.obs, torch.from_numpy(obs)), (tb.actions, actions), (tb.logp, logp), (tb.values, values),
                      (tb.returns, returns), (tb.adv, adv)):
         dst.copy_(src)
-    perms = [torch.randperm(B, generator=torch.Generator().manual_seed(seed * 10 + e)) for e in range(E)]
-    return args, spec, tb, pols, (obs, actions, logp, values, returns, adv), perms
+
+
+def _update_setup(env, P, T, N, E, M, seed, **kw):
+    args = small_args(env, num_steps=T, num_processes=N, ppo_epoch=E, num_mini_batch=M)
+    spec, tb, pols = _batch_with_policies(env, P, N, T, seed=seed, scale=0.05, ppo_epoch=E, num_mini_batch=M, **kw)
+    data, perms = _update_data(spec, pols, T, N, E, seed)
+    _load_update_data(tb, data)
+    return args, spec, tb, pols, data, perms
 
 
 @pytest.mark.parametrize('kernel', ['t16x4', 'mfma', 'mfma-tower', 'mfma-joint', 'valu'])
@@ -217,8 +230,10 @@ def test_ppo_update(gpu, env, T, N, E, M, kernel, monkeypatch):
 @pytest.mark.parametrize('env,T,N,E,M', [('MO-Humanoid-v2', 64, 8, 2, 4), ('MO-Humanoid-v2', 50, 3, 1, 3),
                                          ('MO-Humanoid-v2', 128, 8, 1, 2), ('MO-Humanoid-v2', 256, 8, 1, 32)])
 def test_ppo_update_wide(gpu, env, T, N, E, M, monkeypatch):
-    # obs_dim 376: layer 1 from L2, dW1 running sums in the workspace (pgm_ppo_wide.hip); ragged (mb = 50),
-    # one-pass (mb = 128) and multi-pass (mb = 512) minibatches
+    # obs_dim 376 (pgm_ppo_wide.hip) on two workgroups per tower: layer 1 streamed from each workgroup's private
+    # k-quad copy in the workspace, dW1 in registers, the parts' gradient images summed through the exchange slots;
+    # ragged (mb = 50), one-pass (mb = 128) and multi-pass (mb = 512) minibatches.  The other placements and the
+    # minibatch edges: tests/test_gpu_wide_update.py
     test_ppo_update(gpu, env, T, N, E, M, 'mfma', monkeypatch)
 
 

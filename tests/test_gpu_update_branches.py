@@ -2,7 +2,8 @@
 
 Eight kernels -- the feature-split kernel (pgm_ppo_fs.hip), the four row-split placements (pgm_ppo_mfma.hip: 16-row
 tiles on four workgroups per tower, MODE 2 / 1 / 0), the VALU kernel (pgm_ppo_update.hip), the wide Humanoid kernel
-(pgm_ppo_wide.hip) and the LayerNorm kernel (pgm_ppo_ln.hip) -- each read pgm_ppo_hparams on their own and each wire
+(pgm_ppo_wide.hip, at each of its placements: 4, 2 and 1 workgroups per tower) and the LayerNorm kernel
+(pgm_ppo_ln.hip) -- each read pgm_ppo_hparams on their own and each wire
 the clipped surrogate, the clipped value loss, clip_grad_norm_ and Adam (a2c_ppo_acktr/algo/ppo.py:76-103) into their
 own tiles.  The arithmetic is shared where that left the register-critical kernels' code unchanged
 (pgm_ppo_terms.hpp, tested on the CPU by tests/test_ppo_terms.py) and restated at the sites DESIGN.md 19 lists, so
@@ -37,7 +38,10 @@ KERNELS = {
     'mfma1': ('mfma', '1', 'ppo_update_mfma_kernel (MODE 1)', ('hopper2', 'hopper3', 'walker')),
     'mfma0': ('mfma', '0', 'ppo_update_mfma_kernel (MODE 0)', ('hopper2', 'hopper3', 'walker')),
     'valu': ('valu', None, 'ppo_update_kernel (VALU, A/B)', ('hopper2', 'hopper3')),
-    'wide': (None, None, 'ppo_update_wide_kernel (', ('humanoid32', 'humanoid50')),
+    # the wide kernel's three placements: NS = 4 workgroups per tower (the launcher's own choice at these P), 2 and 1
+    'wide': (None, None, 'ppo_update_wide_kernel (NS=4)', ('humanoid32', 'humanoid50')),
+    'wide2': (None, '2', 'ppo_update_wide_kernel (NS=2)', ('humanoid32', 'humanoid50')),
+    'wide1': (None, '1', 'ppo_update_wide_kernel (NS=1)', ('humanoid32', 'humanoid50')),
     'ln': (None, None, 'ppo_update_ln_kernel (', ('hopper2', 'hopper3')),
 }
 MATRIX = [(k, s, 'a') for k, v in KERNELS.items() for s in v[3]] + \

@@ -10,31 +10,32 @@ i.e. one iteration of MOPG_worker's loop body (morl/mopg.py:95-155) for all task
 torch is used only for device memory and the stream; every op is a libpgm kernel and raises if
 the library is unavailable (no CPU fallback).
 
-With ``host_env`` (a ``hostenv.HostVecEnv``) the environments run on the host instead: the rollout becomes a per-step
-loop of pgm_rollout_act -> host ``step`` -> pgm_env_ingest and the evaluation a host episode loop over pgm_eval_act;
-returns, advantages and the PPO update are the same kernels on the same storage.
+How the env is stepped is the batch's env mode (``tb.mode``); which policy / update kernels act on the storage is its
+kernel family (``tb.family``).  Returns, advantages and the statistics are the same kernels on the same storage in every
+combination (the table of combinations, and where a new mode or family plugs in).
 
-With ``device_env=True`` on Deep Sea Treasure (the one discrete-action env with a device form) the rollout is again one
-launch, pgm_rollout_dst, and the evaluation pgm_eval_dst: the kernel sequence of the continuous device envs with the
-Categorical head and the grid world stepped inside the kernels.
-
-The MO-Dummy envs (envspec.native_env_names(): the reference's MuJoCo-free continuous env) are device envs by default,
-like SynthMO: the rollout is pgm_rollout_dummy, the evaluation pgm_eval_dummy, everything else the Gaussian kernels.
-``host_env=hostenv.DummyMOHostVecEnv(...)`` selects the host-stepped path instead.
-
-With ``env_plugin`` (an ``envplug.EnvPlugin`` or the path of a user env header, include/pgm_envplug.h) the env is the
-user's own: the rollout is pgm_envplug_rollout and the evaluation pgm_envplug_eval of the plug-in's library, one launch
-each, and returns, advantages and the PPO update are the runtime-dim kernels of libpgm.so on the same storage.  A
-contract-2 header (runtime parameters ``env_params``, per-step uniforms) goes through pgm_envplug_rollout_ex /
-pgm_envplug_eval_ex.
+Env modes:
+  * ``SynthMode``: the SynthMO device envs, pgm_env_reset / pgm_rollout / pgm_eval; with ``run_seeds`` (the tasks of
+    several runs in one population) the *_runs entry points;
+  * ``HostMode``: ``host_env`` (a ``hostenv.HostVecEnv``) steps the envs on the host: the rollout is a per-step loop of
+    rollout_act -> host ``step`` -> env_ingest, the evaluation a host episode loop over eval_act;
+  * ``DstMode``: ``device_env=True`` on Deep Sea Treasure, the one discrete-action env with a device form:
+    pgm_rollout_dst / pgm_eval_dst, one launch each, the grid world stepped inside the kernels;
+  * ``DummyMode``: the MO-Dummy envs (envspec.native_env_names()), device envs by default: pgm_rollout_dummy /
+    pgm_eval_dummy (``host_env=hostenv.DummyMOHostVecEnv(...)`` selects HostMode instead);
+  * ``PluginMode``: ``env_plugin`` (an ``envplug.EnvPlugin`` or the path of a user env header, include/pgm_envplug.h):
+    pgm_envplug_rollout / pgm_envplug_eval of the plug-in's library, *_ex for a contract-2 header.
+Kernel families (``FAMILIES``): 'gauss' (compiled per dim set, Gaussian head, plain or LayerNorm towers), 'cat' (the
+Categorical *_cat entry points), 'any' (the runtime-dim *_any entry points, either head).
 """
 import ctypes as C
-import math
+import time
+from collections import namedtuple
 
 import numpy as np
 import torch
 
-from . import envspec
+from . import envplug, envspec
 from ._lib import (ANY_MAX_ACT, ANY_MAX_OBJ, ANY_MAX_OBS, Dims, DstSpec, DummySpec, EnvSpec, EnvState, NormState,
                    PGMError, PPOHParams, RolloutBuf, check, launch_opts, lib, require_any_dims, require_categorical,
                    require_dst_device, require_dummy_device, require_runs, require_tasks, TASK_HPARAM_FIELDS)
@@ -42,8 +43,10 @@ from .layout import ParamLayout
 
 F32, F64, I32 = torch.float32, torch.float64, torch.int32
 LN_MAX_OBS = 32  # layernorm=True: the five envs with obs_dim <= 32 (include/pgm_abi.h pgm_dims.LN)
+HOST_EVAL_MAX = 8  # pgm_eval_act and the fused evaluations: evaluation episodes per task in one launch
 UPDATE_TIMEOUT_MSG = ('pgm_ppo_update: a cross-workgroup exchange timed out (workspace word 2P set); the update '
                       'kernel\'s workgroups were not co-resident -- the parameters are invalid')
+ENV_NOISE_MSG = 'rollout(env_noise=...): only a contract-2 env plug-in with NW > 0 takes env noise'
 
 
 # the per-task settings of set_task_hparams: pgm_task_hparams' fields in order, then the GAE lambda
@@ -76,6 +79,425 @@ def _stream():
     return C.c_void_p(torch.cuda.current_stream().cuda_stream)
 
 
+def _call(name, *args, of=None):
+    """Entry point `name` of libpgm.so, or of the plug-in `of`, on the current stream (every launch ends with it)."""
+    if of is None:
+        check(getattr(lib(), name)(*args, _stream()), name)
+    else:
+        of.check(getattr(of.h, name)(*args, _stream()), name)
+
+
+# ---------------------------------------------------------------------------------------------- kernel families
+# The entry points of one family of policy / update kernels and what their calls look like.  head: the act, evaluation
+# and update calls take the head type (0 Gaussian, 1 Categorical) after the dims; tasks: the per-task-settings update
+# pgm_ppo_update_tasks (and pgm_gae_tasks) exists; opts: the update takes launch_opts and pgm_ppo_update_reset clears
+# its workspace (the others reset their own, smaller one); variant: update_variant() where there is no launch choice
+Family = namedtuple('Family', 'rollout_act env_ingest eval_act ppo_update workspace_bytes head tasks opts variant')
+
+
+def _family(sfx, env_ingest, head=False, gauss=False, variant=None):
+    return Family(f'pgm_rollout_act{sfx}', env_ingest, f'pgm_eval_act{sfx}', f'pgm_ppo_update{sfx}',
+                  f'pgm_ppo_update{sfx}_workspace_bytes', head, gauss, gauss, variant)
+
+
+FAMILIES = {'gauss': _family('', 'pgm_env_ingest', gauss=True),
+            'cat': _family('_cat', 'pgm_env_ingest', variant='ppo_update_cat_kernel (one workgroup per tower)'),
+            'any': _family('_any', 'pgm_env_ingest_any', head=True, variant='ppo_update_any_kernel')}
+
+
+# ---------------------------------------------------------------------------------------------- env modes
+class EnvMode:
+    """One way of stepping the env.  A mode owns its constructor checks, defaults and allocations (``setup``: per-task
+    tensors through ``tb.z``, mode-wide constants on the mode), what it rebuilds per ``set_active`` (``views``) and the
+    operations ``reset`` / ``rollout`` / ``evaluate``; the facts below are all the batch's other methods know of it."""
+    name = None          # what set_task_hparams' refusal calls the mode (None: SynthMode, which has the settings)
+    no_step = None       # env_step's refusal (None: the mode has the single-step kernel)
+    fused_noise = False  # the rollout draws its action noise in-kernel: iteration() pre-draws none
+    overlap = True       # the evaluation is a launch that can run beside the next rollout
+    run_seeds = plugin = None
+
+    def setup(self, tb, **kw):
+        pass
+
+    def views(self, tb):
+        pass
+
+    def _noise(self, tb, noise, env_noise, takes_env_noise=False):
+        """A fused rollout's noise argument: explicit noise uploaded into tb.noise; None: the kernel draws the stream."""
+        if env_noise is not None and not takes_env_noise:
+            raise PGMError(ENV_NOISE_MSG)
+        if noise is None:
+            return None
+        if noise is not tb.noise:
+            tb.noise.copy_(noise.to(dtype=F32))
+        return tb.noise
+
+    @staticmethod
+    def _eval_tail(tb, out):
+        return tb.eval_num, int(tb.use_ob_rms), int(tb.raw), tb.gamma, _ptr(out)
+
+
+class SynthMode(EnvMode):
+    """The SynthMO device envs.  run_seeds: the reset tables are stacked per run, task p resets from the block of run
+    ``tb.run_of_task[p]`` and every operation goes through its *_runs entry point."""
+
+    def __init__(self, env_name, run_seeds, **other_modes):
+        if run_seeds is None:
+            return
+        self.run_seeds = [int(x) for x in run_seeds]
+        if not self.run_seeds:
+            raise PGMError('run_seeds=[]: a multi-run batch needs at least one seed')
+        for flag, on in other_modes.items():
+            if on:
+                raise PGMError(f'run_seeds=... with {flag}=...: several runs share one population on the SynthMO '
+                               f'device envs only (the reset tables of {flag} have another shape)')
+        sp = envspec.make_spec(env_name)
+        if sp.get('native') == 'dummy' or sp.get('discrete') or sp.get('user'):
+            raise PGMError(f'run_seeds=... with {env_name}: several runs share one population on the SynthMO '
+                           f'device envs only (the MO-Dummy / Deep Sea Treasure reset tables are per family)')
+        require_runs()
+        self.no_step = ('env_step: a multi-run batch (run_seeds=...) has no single-step kernel that takes the reset '
+                        'rows per task; the envs are stepped inside rollout()')
+
+    def setup(self, tb, **kw):
+        if self.run_seeds is not None:  # every task starts in run 0
+            tb.run_of_task = torch.zeros(tb.capacity, dtype=I32, device=tb.dev)
+
+    def _runs(self, tb):
+        return ('_runs', (_ptr(tb.run_of_task), len(self.run_seeds))) if self.run_seeds is not None else ('', ())
+
+    def reset(self, tb):
+        sfx, runs = self._runs(tb)
+        out = torch.empty(tb.P, tb.N, tb.O, dtype=F32, device=tb.dev)
+        _call('pgm_env_reset' + sfx, C.byref(tb.dims), C.byref(tb.c_spec), C.byref(tb.c_state), C.byref(tb.c_norm),
+              *runs, _ptr(out))
+        tb.obs[:, 0].copy_(out)
+        tb.masks[:, 0] = 1.0
+        tb.bad_masks[:, 0] = 1.0
+        return out
+
+    def rollout(self, tb, seed, noise, carry, env_noise):
+        sfx, runs = self._runs(tb)
+        nz = self._noise(tb, noise, env_noise)
+        _call('pgm_rollout' + sfx, C.byref(tb.dims), _ptr(tb.params), C.byref(tb.c_spec), C.byref(tb.c_state),
+              C.byref(tb.c_norm), C.byref(tb.c_rb), _ptr(nz), C.c_uint64(seed), int(carry), *runs,
+              C.byref(launch_opts()))
+
+    def evaluate(self, tb, mean, var, out):
+        sfx, runs = self._runs(tb)
+        _call('pgm_eval' + sfx, C.byref(tb.dims), _ptr(tb.params), C.byref(tb.c_spec), _ptr(mean), _ptr(var),
+              _ptr(tb.s0_eval), *self._eval_tail(tb, out), *runs, C.byref(launch_opts()))
+
+
+class HostMode(EnvMode):
+    """``tb.host_env`` steps the envs on the host; the device acts, ingests and evaluates with the family's
+    rollout_act / env_ingest / eval_act kernels."""
+    name = 'host_env'
+    overlap = False  # the evaluation is a host episode loop that synchronises every step
+
+    def setup(self, tb, **kw):
+        """Pinned host / device staging: the sampled actions (D2H; discrete: int32 indices) and one packed fp64 record
+        per step -- raw obs | raw objectives | reward | done, bad_transition as int32 pairs -- so H2D is one copy."""
+        he, Pc, N, O, A, K, E = tb.host_env, tb.capacity, tb.N, tb.O, tb.A, tb.K, tb.eval_num
+        if tuple(he.dims()) != (O, A, K) or he.N != N:
+            raise PGMError(f'host_env has (obs, act, obj) dims {tuple(he.dims())} and {he.N} envs per task; '
+                           f'{tb.env_name} with num_processes={N} needs {(O, A, K)} and {N}')
+        if getattr(he, 'capacity', he.P) < Pc:
+            raise PGMError(f'host_env holds {getattr(he, "capacity", he.P)} tasks, the batch needs {Pc}')
+        if E > HOST_EVAL_MAX:
+            raise PGMError(f'host-env mode evaluates at most {HOST_EVAL_MAX} episodes per task (eval_num={E})')
+        if bool(getattr(he, 'discrete', False)) != tb.discrete:
+            raise PGMError(f'host_env.discrete = {getattr(he, "discrete", False)} but {tb.env_name} has '
+                           f'{"discrete" if tb.discrete else "continuous"} actions')
+        self.no_step = ('env_step: this batch runs on the runtime-dim kernels, which are host-stepped only: the '
+                        'environments are stepped inside rollout(), there is no device env to step' if tb.any_dims else
+                        'env_step: this batch is in host-env mode (TaskBatch(host_env=...)): the environments are '
+                        'stepped on the host inside rollout(), there is no device env to step')
+        ashape, adt = ((Pc, N), I32) if tb.discrete else ((Pc, N, A), F32)
+        self._h_act = torch.empty(ashape, dtype=adt, pin_memory=True)
+        self._d_act = torch.zeros(ashape, dtype=adt, device=tb.dev)
+        n = Pc * N * (O + K + 2)
+        self._h_tr = torch.zeros(n, dtype=F64, pin_memory=True)
+        self._d_tr = torch.zeros(n, dtype=F64, device=tb.dev)
+        self._tr_ready = None  # the last H2D copy out of _h_tr (the host waits for it before rewriting the buffer)
+        self._h_eobs = torch.zeros(Pc * E * O, dtype=F64, pin_memory=True)
+        self._d_eobs = torch.zeros(Pc * E * O, dtype=F64, device=tb.dev)
+        self._h_eact = torch.empty(Pc * E * tb.act_width, dtype=adt, pin_memory=True)
+        self._d_eact = torch.zeros(Pc * E * tb.act_width, dtype=adt, device=tb.dev)
+
+    def views(self, tb):
+        P, N, O, K = tb.P, tb.N, tb.O, tb.K
+        n1, n2, n3 = P * N * O, P * N * K, P * N
+
+        def seg(buf):
+            flags = buf[n1 + n2 + n3:n1 + n2 + 2 * n3].view(I32).view(2, P, N)
+            return (buf[:n1].view(P, N, O), buf[n1:n1 + n2].view(P, N, K), buf[n1 + n2:n1 + n2 + n3].view(P, N),
+                    flags[0], flags[1])
+        self._tr_len = n1 + n2 + 2 * n3
+        self._d_seg = seg(self._d_tr)
+        self._h_seg = tuple(v.numpy() for v in seg(self._h_tr))
+        tb.host_env.set_active(P)
+
+    def stage(self, t, obs, rew, done, bad, obj):
+        """One packed H2D copy of the host transition (t = -1: the reset observation alone); returns the device views."""
+        if self._tr_ready is not None:
+            self._tr_ready.synchronize()
+        ho, hj, hr, hd, hb = self._h_seg
+        ho[...] = obs
+        if t >= 0:
+            hj[...], hr[...], hd[...], hb[...] = obj, rew, done, bad
+        n = self._tr_len
+        self._d_tr[:n].copy_(self._h_tr[:n], non_blocking=True)
+        self._tr_ready = torch.cuda.Event()
+        self._tr_ready.record()
+        return self._d_seg
+
+    def reset(self, tb):  # one H2D copy of the host envs' reset observations, then the ingest kernel
+        tb._ingest(-1, tb.host_env.reset())
+
+    def rollout(self, tb, seed, noise, carry, env_noise):
+        """morl/mopg.py:103-135 with the env on the host: per step t the device acts on obs[t], the actions go to the
+        host (pinned D2H + the step's one stream synchronise), the host envs step, the transition returns (pinned
+        H2D) and the device applies VecNormalize + insert into slot t + 1; then the bootstrap value."""
+        P, T, he = tb.P, tb.T, tb.host_env
+        if hasattr(he, 'begin_rollout'):  # a host-stepped contract-2 plug-in: this rollout's env noise
+            he.begin_rollout(envplug.env_seed(seed), None if env_noise is None else
+                             torch.as_tensor(env_noise).detach().cpu().numpy())
+        elif env_noise is not None:
+            raise PGMError(ENV_NOISE_MSG)
+        if noise is None:  # the perf-mode counter stream of `seed`: what the fused rollout draws in-kernel
+            tb._draw_noise(seed)
+        elif noise is not tb.noise:
+            tb.noise.copy_(noise.to(dtype=F32))
+        if carry:  # after_update(): slot T -> slot 0 (storage.py:71-75)
+            tb.obs[:, 0].copy_(tb.obs[:, T])
+            tb.masks[:, 0].copy_(tb.masks[:, T])
+            tb.bad_masks[:, 0].copy_(tb.bad_masks[:, T])
+        stream = torch.cuda.current_stream()
+        prof = tb.host_profile
+        h_act = self._h_act[:P]
+        a_np = h_act.numpy()
+        for t in range(T):
+            t0 = time.perf_counter()
+            tb._rollout_act(t)
+            h_act.copy_(self._d_act[:P], non_blocking=True)
+            stream.synchronize()
+            t1 = time.perf_counter()
+            obs, rew, done, bad, obj = he.step(a_np)
+            t2 = time.perf_counter()
+            tb._ingest(t, obs, rew, done, bad, obj)
+            if prof is not None:
+                stream.synchronize()  # (only when timed: the ingest otherwise overlaps nothing the host waits for)
+                prof['act'] += t1 - t0
+                prof['step'] += t2 - t1
+                prof['ingest'] += time.perf_counter() - t2
+        tb._rollout_act(T)
+
+    def evaluate(self, tb, mean, var, out):
+        """evaluation() (morl/mopg.py:25-46) with the episodes on the host: eval_num episodes per task step together,
+        eval_act normalises with the frozen statistics and returns the deterministic actions (discrete: int32 action
+        indices [P, E]); an ended episode stops contributing."""
+        P, E, O, K, A, he = tb.P, tb.eval_num, tb.O, tb.K, tb.act_width, tb.host_env
+        stream = torch.cuda.current_stream()
+        h_obs, h_act = self._h_eobs[:P * E * O], self._h_eact[:P * E * A]
+        obs_np = h_obs.numpy().reshape(P, E, O)
+        act_np = h_act.numpy().reshape((P, E) if tb.discrete else (P, E, A))
+        acc = np.zeros((P, E, K))
+        disc = 1.0
+        alive = np.ones((P, E), dtype=bool)
+        obs = he.eval_reset(E)
+        d = Dims(P, 1, 0, O, tb.A, K, tb.H, int(tb.layernorm))
+        while alive.any():
+            obs_np[...] = obs
+            self._d_eobs[:P * E * O].copy_(h_obs, non_blocking=True)
+            tb._launch(tb.family.eval_act, d, _ptr(tb.params), _ptr(mean), _ptr(var), int(tb.use_ob_rms),
+                       _ptr(self._d_eobs), E, _ptr(self._d_eact))
+            h_act.copy_(self._d_eact[:P * E * A], non_blocking=True)
+            stream.synchronize()
+            obs, obj, done = he.eval_step(act_np)
+            acc += np.where(alive[..., None], disc * np.asarray(obj, dtype=np.float64), 0.0)
+            if not tb.raw:
+                disc *= tb.gamma
+            alive &= ~np.asarray(done, dtype=bool)
+        out.copy_(torch.from_numpy(acc.sum(1) / E))
+
+
+class DstMode(EnvMode):
+    """Deep Sea Treasure stepped inside pgm_rollout_dst / pgm_eval_dst.  max_steps / time_limit_is_bad: the step limit
+    and whether it is reported as a time-limit end, as hostenv.DeepSeaTreasureHostVecEnv has them."""
+    name = 'device_env'
+    no_step = ('env_step: the device Deep Sea Treasure is stepped inside pgm_rollout_dst / pgm_eval_dst; '
+               'there is no single-step kernel (pgm_dst_transition evaluates the rule on the host)')
+    fused_noise = True
+
+    def setup(self, tb, max_steps, time_limit_is_bad, **kw):
+        if (tb.O, tb.A, tb.K) != (3, 4, 2):
+            raise PGMError(f'device_env=True with {tb.env_name}: the one discrete-action device env is Deep Sea '
+                           f'Treasure (obs 3, 4 actions, 2 objectives)')
+        if not 1 <= tb.eval_num <= HOST_EVAL_MAX:
+            raise PGMError(f'device_env=True evaluates 1..{HOST_EVAL_MAX} episodes per task in one launch '
+                           f'(eval_num={tb.eval_num})')
+        require_dst_device()
+        self.max_steps = int(max_steps or tb.spec['max_episode_steps'])
+        self.time_limit_is_bad = bool(time_limit_is_bad)
+        self.c_dst = DstSpec(self.max_steps, int(self.time_limit_is_bad))
+        # the constant raw reset observation of (row, col, step) = (0, 0, 0), for env_ingest(-1)
+        self._dst_obs0 = torch.zeros(tb.capacity, tb.N, tb.O, dtype=F64, device=tb.dev)
+
+    def reset(self, tb):  # every env at (0, 0, 0); VecNormalize.reset on the constant reset observation
+        tb.s.zero_()
+        tb._env_ingest(-1, self._dst_obs0)
+
+    def rollout(self, tb, seed, noise, carry, env_noise):
+        nz = self._noise(tb, noise, env_noise)
+        _call('pgm_rollout_dst', C.byref(tb.dims), _ptr(tb.params), C.byref(self.c_dst), C.byref(tb.c_state),
+              C.byref(tb.c_norm), C.byref(tb.c_rb), _ptr(nz), C.c_uint64(seed), int(carry))
+
+    def evaluate(self, tb, mean, var, out):
+        _call('pgm_eval_dst', C.byref(tb.dims), _ptr(tb.params), C.byref(self.c_dst), _ptr(mean), _ptr(var),
+              *self._eval_tail(tb, out))
+
+
+class DummyMode(EnvMode):
+    """An MO-Dummy env stepped inside pgm_rollout_dummy / pgm_eval_dummy.  max_steps (default 500), bound (5.0),
+    time_limit_is_bad (default True: the registration's TimeLimitMask) and R (reset positions per env, default
+    envspec.DUMMY_RESETS) are the device env's, as hostenv.DummyMOHostVecEnv has them."""
+    name = 'an MO-Dummy env'
+    fused_noise = True
+
+    def setup(self, tb, seed, max_steps, time_limit_is_bad, bound, R, **kw):
+        env_name, sp, N, E = tb.env_name, tb.spec, tb.N, tb.eval_num
+        if not 1 <= E <= HOST_EVAL_MAX:
+            raise PGMError(f'{env_name} evaluates 1..{HOST_EVAL_MAX} episodes per task in one launch (eval_num={E})')
+        if N > 8:
+            raise PGMError(f'{env_name}: num_processes={N} envs per task > 8 unsupported')
+        self.max_steps = int(max_steps or sp['max_episode_steps'])
+        self.bound = float(sp['bound'] if bound is None else bound)
+        self.time_limit_is_bad = True if time_limit_is_bad is None else bool(time_limit_is_bad)
+        self.R = int(envspec.DUMMY_RESETS if R is None else R)
+        if self.max_steps <= 0 or not self.bound > 0 or self.R < 1:
+            raise PGMError(f'{env_name}: max_steps={self.max_steps}, bound={self.bound} and R={self.R} must be '
+                           f'positive')
+        self.no_step = (f'env_step: {env_name} is stepped inside pgm_rollout_dummy / pgm_eval_dummy; there is '
+                        f'no single-step kernel (pgm_dummy_transition evaluates the rule on the host)')
+        # per (task, env): resets since env_reset(); the reset positions [N][R][2], [eval_num][R][2]
+        tb.z('episode', N, dt=I32)
+        self._dummy_train = torch.tensor(envspec.dummy_reset_table(seed, N, self.R), dtype=F64, device=tb.dev)
+        self._dummy_eval = torch.tensor(envspec.dummy_reset_table(seed, E, self.R), dtype=F64, device=tb.dev)
+
+    def views(self, tb):
+        tlb = int(self.time_limit_is_bad)
+        self.c_dummy = DummySpec(self.max_steps, tlb, self.bound, _ptr(self._dummy_train), self.R, tb.N)
+        self.c_dummy_eval = DummySpec(self.max_steps, tlb, self.bound, _ptr(self._dummy_eval), self.R, tb.eval_num)
+
+    def reset(self, tb):  # env n of every task at entry (n, 0) of the reset table, at rest; VecNormalize.reset
+        tb.s.zero_()
+        tb.s[:, :, :2] = self._dummy_train[:, 0]
+        tb.elapsed.zero_()
+        tb.episode.zero_()
+        tb._env_ingest(-1, tb.s)
+
+    def rollout(self, tb, seed, noise, carry, env_noise):
+        nz = self._noise(tb, noise, env_noise)
+        _call('pgm_rollout_dummy', C.byref(tb.dims), _ptr(tb.params), C.byref(self.c_dummy), C.byref(tb.c_state),
+              _ptr(tb.episode), C.byref(tb.c_norm), C.byref(tb.c_rb), _ptr(nz), C.c_uint64(seed), int(carry))
+
+    def evaluate(self, tb, mean, var, out):
+        _call('pgm_eval_dummy', C.byref(tb.dims), _ptr(tb.params), C.byref(self.c_dummy_eval), _ptr(mean), _ptr(var),
+              *self._eval_tail(tb, out))
+
+
+class PluginMode(EnvMode):
+    """A device env plug-in: env_name is registered with the header's dims, the env stepped inside the fused kernels of
+    its library.  R: reset-table entries per env (default envplug.DEFAULT_RESETS).  A contract-2 header's per-step
+    uniforms come from the stream of envplug.env_seed(rollout seed); the evaluation's from tb._plug_eval_seed =
+    envplug.env_seed(seed): fixed for the batch, so every policy it evaluates meets the same env noise."""
+    name = 'env_plugin'
+    no_step = ('env_step: an env plug-in is stepped inside pgm_envplug_rollout / pgm_envplug_eval; there '
+               'is no single-step kernel (EnvPlugin.transition evaluates the header on the host)')
+    fused_noise = True
+
+    def __init__(self, env_name, env_plugin, env_params, host_env, device_env, layernorm, eval_num, num_processes):
+        if host_env is not None or device_env:
+            raise PGMError('env_plugin=... steps the env inside the plug-in\'s fused kernels: host_env=... and '
+                           'device_env=True are other places to step it; give env_plugin alone (the same header on '
+                           'the host: host_env=hostenv.PluginHostVecEnv(plugin, ...) without env_plugin)')
+        if layernorm:
+            raise PGMError('layernorm=True with env_plugin=...: env plug-ins are built for plain towers only')
+        if eval_num > HOST_EVAL_MAX or eval_num < 1:
+            raise PGMError(f'eval_num={eval_num} with env_plugin=...: a plug-in evaluates 1..{HOST_EVAL_MAX} '
+                           f'episodes per task in one launch')
+        if num_processes > 8:
+            raise PGMError(f'num_processes={num_processes} with env_plugin=...: envs per task > 8 unsupported')
+        self.plugin = envplug.as_plugin(env_plugin)
+        self._plug_par_np = self.plugin.par_vector(env_params)  # (refuses unknown names, NP == 0)
+        try:
+            self.plugin.register(env_name)
+        except ValueError as e:
+            raise PGMError(f'env_plugin=...: {e}') from e
+
+    def setup(self, tb, seed, R, **kw):
+        pl, N, dims = self.plugin, tb.N, (tb.O, tb.A, tb.K)
+        if pl.dims() != dims or pl.DISCRETE != tb.discrete:
+            raise PGMError(f'env_plugin has (obs, act, obj) dims {pl.dims()}, discrete = {pl.DISCRETE}; '
+                           f'{tb.env_name} is registered with {dims}, discrete = {tb.discrete}')
+        self.R = int(envplug.DEFAULT_RESETS if R is None else R)
+        if self.R < 1:
+            raise PGMError(f'{tb.env_name}: R={self.R} reset-table entries per env must be at least 1')
+        # the plug-in's state words, resets since env_reset(), the reset uniforms
+        tb.z('plug_sd', N, pl.SD, dt=F64)
+        tb.z('plug_si', N, pl.SI, dt=I32)
+        tb.z('episode', N, dt=I32)
+        self._plug_train_np = envspec.plugin_reset_table(seed, N, self.R, pl.RW)
+        self._plug_train = torch.tensor(self._plug_train_np, dtype=F64, device=tb.dev)
+        self._plug_eval = torch.tensor(envspec.plugin_reset_table(seed, tb.eval_num, self.R, pl.RW), dtype=F64,
+                                       device=tb.dev)
+        self._plug_obs0 = torch.zeros(tb.capacity, N, tb.O, dtype=F64, device=tb.dev)
+        self._plug_par = torch.tensor(self._plug_par_np if pl.NP else [0.0], dtype=F64, device=tb.dev)
+        tb.env_noise = None  # [T][N][NW] fp64, allocated by the first rollout that is fed its env noise
+        tb._plug_eval_seed = envplug.env_seed(seed)
+
+    def reset(self, tb):  # env n of every task at entry (n, 0) of its row: the header's reset on the host
+        P, N, pl = tb.P, tb.N, self.plugin
+        row = np.broadcast_to(np.arange(N, dtype=np.int32), (P, N)).reshape(-1)
+        sd, si, obs = pl.reset(row, np.zeros(P * N, dtype=np.int32), self._plug_train_np, par=self._plug_par_np)
+        tb.plug_sd.copy_(torch.from_numpy(sd.reshape(P, N, pl.SD)))
+        tb.plug_si.copy_(torch.from_numpy(si.reshape(P, N, pl.SI)))
+        self._plug_obs0[:P].copy_(torch.from_numpy(obs.reshape(P, N, tb.O)))
+        tb.elapsed.zero_()
+        tb.episode.zero_()
+        tb._env_ingest(-1, self._plug_obs0)
+
+    def rollout(self, tb, seed, noise, carry, env_noise):
+        pl = self.plugin
+        nz = self._noise(tb, noise, env_noise, takes_env_noise=pl.NW > 0)
+        args = (C.byref(tb.dims), _ptr(tb.params), _ptr(tb.plug_sd), _ptr(tb.plug_si), _ptr(tb.episode),
+                _ptr(self._plug_train), self.R, tb.N, C.byref(tb.c_state), C.byref(tb.c_norm), C.byref(tb.c_rb),
+                _ptr(nz), C.c_uint64(seed), int(carry))
+        if pl.CONTRACT == 1:
+            return _call('pgm_envplug_rollout', *args, of=pl)
+        ez = None
+        if env_noise is not None:
+            shape = (tb.T, tb.N, pl.NW)
+            if tuple(env_noise.shape) != shape:
+                raise PGMError(f'rollout(env_noise=...) of shape {tuple(env_noise.shape)}: this batch steps '
+                               f'[T][N][NW] = {shape}')
+            if tb.env_noise is None:
+                tb.env_noise = torch.zeros(shape, dtype=F64, device=tb.dev)
+            tb.env_noise.copy_(torch.as_tensor(env_noise).to(dtype=F64))
+            ez = tb.env_noise
+        _call('pgm_envplug_rollout_ex', *args, _ptr(self._plug_par), _ptr(ez), C.c_uint64(envplug.env_seed(seed)),
+              of=pl)
+
+    def evaluate(self, tb, mean, var, out):
+        pl = self.plugin
+        args = (C.byref(tb.dims), _ptr(tb.params), _ptr(self._plug_eval), self.R, tb.eval_num, _ptr(mean), _ptr(var),
+                *self._eval_tail(tb, out))
+        if pl.CONTRACT == 1:
+            return _call('pgm_envplug_eval', *args, of=pl)
+        _call('pgm_envplug_eval_ex', *args, _ptr(self._plug_par), C.c_uint64(tb._plug_eval_seed), of=pl)
+
+
 class TaskBatch:
     """HBM state of P tasks sharing env, rollout shape and PPO hyper-parameters.
 
@@ -90,6 +512,7 @@ class TaskBatch:
     # (name, width per task: int, or the attribute of the dims it is); the order is the stats64 layout
     STAT_SEGMENTS = (('weights', 'K'), ('ob_mean', 'O'), ('ob_var', 'O'), ('ob_count', 0), ('ret_mean', 0),
                      ('ret_var', 0), ('ret_count', 0), ('obj_mean', 'K'), ('obj_var', 'K'), ('obj_count', 0))
+    HOST_EVAL_MAX = HOST_EVAL_MAX
 
     def __init__(self, env_name, P, num_processes=4, num_steps=2048, seed=0, eval_num=1, gamma=0.995,
                  gae_lambda=0.95, use_gae=True, use_proper_time_limits=True, ob_rms=True, obj_rms=True, raw=True,
@@ -97,67 +520,26 @@ class TaskBatch:
                  max_grad_norm=0.5, adam_eps=1e-5, use_clipped_value_loss=True, device='cuda', capacity=None,
                  layernorm=False, host_env=None, device_env=False, *, max_steps=None, time_limit_is_bad=None,
                  bound=None, R=None, any_dims=False, env_plugin=None, run_seeds=None, env_params=None):
-        """device_env: run a discrete-action env on the device (Deep Sea Treasure: pgm_rollout_dst / pgm_eval_dst)
-        instead of on the host; for such an env exactly one of host_env and device_env=True is given.  The SynthMO envs
-        are device envs already: the flag changes nothing there.  max_steps / time_limit_is_bad: the device Deep Sea
-        Treasure's step limit (default envspec's, 50) and whether the limit is reported as a time-limit end, as
-        hostenv.DeepSeaTreasureHostVecEnv has them.  An MO-Dummy env is a device env by default (device_env changes
-        nothing); max_steps (default 500), bound (5.0), time_limit_is_bad (here default True: the registration's
-        TimeLimitMask) and R (reset positions per env, default envspec.DUMMY_RESETS) are the device env's, as
-        hostenv.DummyMOHostVecEnv has them.  any_dims=True: run a host-stepped batch of an env envspec knows on the
-        runtime-dim kernels (the *_any entry points) instead of the ones compiled for its dims; a registered
-        third-party env (envspec.register_env) always runs on them.  env_plugin: a device env plug-in
-        (envplug.EnvPlugin, or the path of its header): env_name is registered with the header's dims, the batch is a
-        runtime-dim batch whose rollout and evaluation are the plug-in library's fused kernels, on the device envs'
-        schedule (overlapped evaluation included); R: reset-table entries per env (default envplug.DEFAULT_RESETS).
+        """device_env: run a discrete-action env on the device (DstMode) instead of on the host; for such an env
+        exactly one of host_env and device_env=True is given.  The SynthMO and MO-Dummy envs are device envs already:
+        the flag changes nothing there.  max_steps / time_limit_is_bad / bound / R: the device env's settings (DstMode,
+        DummyMode, PluginMode).  any_dims=True: run a host-stepped batch of an env envspec knows on the runtime-dim
+        kernels (the *_any entry points) instead of the ones compiled for its dims; a registered third-party env
+        (envspec.register_env) always runs on them.  env_plugin: a device env plug-in (envplug.EnvPlugin, or the path
+        of its header): the batch is a runtime-dim batch on the device envs' schedule (overlapped evaluation included).
         env_params: the runtime parameters of a contract-2 plug-in, a dict name -> float over the header's PAR_NAMES
-        (omitted names take the header's default); one set for every task of the batch.  The plug-in's per-step
-        uniforms come from the stream of envplug.env_seed(rollout seed), the evaluation's from envplug.env_seed(seed):
-        fixed for the batch, so every policy it evaluates meets the same env noise.
-        run_seeds: a list of seeds makes the batch hold the tasks of several runs (a sweep): the reset tables are
-        stacked per run, task p resets from the block of run ``run_of_task[p]`` (set_runs) and env_reset / rollout /
-        evaluate go through the *_runs entry points; `seed` is then unused.  SynthMO device envs only."""
-        self.run_seeds = None
-        if run_seeds is not None:
-            self.run_seeds = [int(x) for x in run_seeds]
-            if not self.run_seeds:
-                raise PGMError('run_seeds=[]: a multi-run batch needs at least one seed')
-            for flag, on in (('host_env', host_env is not None), ('device_env', bool(device_env)),
-                             ('env_plugin', env_plugin is not None)):
-                if on:
-                    raise PGMError(f'run_seeds=... with {flag}=...: several runs share one population on the SynthMO '
-                                   f'device envs only (the reset tables of {flag} have another shape)')
-            sp_ = envspec.make_spec(env_name)
-            if sp_.get('native') == 'dummy' or sp_.get('discrete') or sp_.get('user'):
-                raise PGMError(f'run_seeds=... with {env_name}: several runs share one population on the SynthMO '
-                               f'device envs only (the MO-Dummy / Deep Sea Treasure reset tables are per family)')
-            require_runs()
-        self.plugin = None
+        (omitted names take the header's default); one set for every task of the batch.  run_seeds: a list of seeds
+        makes the batch hold the tasks of several runs (SynthMode, set_runs; SynthMO only); `seed` is then unused."""
+        # the env mode: run_seeds refuses the other modes' flags, env_plugin registers env_name; the rest needs the spec
+        mode = SynthMode(env_name, run_seeds, host_env=host_env is not None, device_env=bool(device_env),
+                         env_plugin=env_plugin is not None)
         if env_plugin is not None:
-            from . import envplug
-            if host_env is not None or device_env:
-                raise PGMError('env_plugin=... steps the env inside the plug-in\'s fused kernels: host_env=... and '
-                               'device_env=True are other places to step it; give env_plugin alone (the same header on '
-                               'the host: host_env=hostenv.PluginHostVecEnv(plugin, ...) without env_plugin)')
-            if layernorm:
-                raise PGMError('layernorm=True with env_plugin=...: env plug-ins are built for plain towers only')
-            if eval_num > self.HOST_EVAL_MAX or eval_num < 1:
-                raise PGMError(f'eval_num={eval_num} with env_plugin=...: a plug-in evaluates 1..{self.HOST_EVAL_MAX} '
-                               f'episodes per task in one launch')
-            if num_processes > 8:
-                raise PGMError(f'num_processes={num_processes} with env_plugin=...: envs per task > 8 unsupported')
-            self.plugin = envplug.as_plugin(env_plugin)
-            self._plug_par_np = self.plugin.par_vector(env_params)  # (refuses unknown names, NP == 0)
-            self._plug_eval_seed = envplug.env_seed(seed)
-            try:
-                self.plugin.register(env_name)
-            except ValueError as e:
-                raise PGMError(f'env_plugin=...: {e}') from e
+            mode = PluginMode(env_name, env_plugin, env_params, host_env, device_env, layernorm, eval_num, num_processes)
         elif env_params:
             raise PGMError('env_params=... sets the runtime parameters of env_plugin=...; this batch has no plug-in (a '
                            'host-stepped plug-in takes them itself: hostenv.PluginHostVecEnv(..., env_params=...))')
-        self.spec = envspec.make_spec(env_name)
-        sp = self.spec
+        self.run_seeds, self.plugin = mode.run_seeds, mode.plugin
+        self.spec = sp = envspec.make_spec(env_name)
         self.host_env = host_env
         self.host_profile = None  # a dict {'act', 'step', 'ingest'} of seconds when a caller wants the split timed
         self.env_name = env_name
@@ -170,7 +552,7 @@ class TaskBatch:
         self.ppo_epoch, self.num_mini_batch = ppo_epoch, num_mini_batch
         self.dev = torch.device(device)
         self.layernorm = bool(layernorm)
-        # the runtime-dim kernel family: host-stepped, plain towers, at most ANY_EVAL_MAX evaluation episodes
+        # the runtime-dim kernel family: host-stepped, plain towers, at most HOST_EVAL_MAX evaluation episodes
         self.any_dims = bool(sp.get('user')) or bool(any_dims)
         if self.any_dims:
             what = f'{env_name} runs on the runtime-dim kernels (a registered third-party env, or any_dims=True)'
@@ -181,8 +563,8 @@ class TaskBatch:
                                f'(hostenv.GymHostVecEnv, --host-env module:callable)')
             if self.layernorm:
                 raise PGMError(f'layernorm=True: {what}, which are built for plain towers only')
-            if eval_num > self.HOST_EVAL_MAX:
-                raise PGMError(f'eval_num={eval_num}: {what}, which evaluate at most {self.HOST_EVAL_MAX} episodes '
+            if eval_num > HOST_EVAL_MAX:
+                raise PGMError(f'eval_num={eval_num}: {what}, which evaluate at most {HOST_EVAL_MAX} episodes '
                                f'per task')
             amin = 2 if sp.get('discrete') else 1
             if not (1 <= self.O <= ANY_MAX_OBS and amin <= self.A <= ANY_MAX_ACT and 1 <= self.K <= ANY_MAX_OBJ):
@@ -194,7 +576,7 @@ class TaskBatch:
                            f'built for obs_dim <= {LN_MAX_OBS}; obs_dim {self.O} would need a streamed layer-1 '
                            f'LayerNorm kernel, which does not exist')
         # a discrete-action env (spec['discrete']): Categorical head, A = number of actions, one width-1 action per
-        # step, the *_cat entry points; such envs run on the host (host_env) or, opted into, on the device (device_env)
+        # step; such envs run on the host (host_env) or, opted into, on the device (device_env)
         self.discrete = bool(sp.get('discrete', False))
         self.device_env = bool(device_env) and self.discrete  # (a SynthMO env is a device env with or without the flag)
         if self.discrete:
@@ -208,64 +590,24 @@ class TaskBatch:
             if self.layernorm:
                 raise PGMError(f'layernorm=True with {env_name}: LayerNorm towers with a Categorical head are not built')
             require_categorical()
-        if self.device_env:
-            if (self.O, self.A, self.K) != (3, 4, 2):
-                raise PGMError(f'device_env=True with {env_name}: the one discrete-action device env is Deep Sea '
-                               f'Treasure (obs 3, 4 actions, 2 objectives)')
-            if not 1 <= eval_num <= self.HOST_EVAL_MAX:
-                raise PGMError(f'device_env=True evaluates 1..{self.HOST_EVAL_MAX} episodes per task in one launch '
-                               f'(eval_num={eval_num})')
-            require_dst_device()
-            self.max_steps = int(max_steps or sp['max_episode_steps'])
-            self.time_limit_is_bad = bool(time_limit_is_bad)
-            self.c_dst = DstSpec(self.max_steps, int(self.time_limit_is_bad))
-        # an MO-Dummy env stepped inside pgm_rollout_dummy / pgm_eval_dummy (the default for these envs)
+        self.family = FAMILIES['any' if self.any_dims else 'cat' if self.discrete else 'gauss']
         self.dummy_env = sp.get('native') == 'dummy' and host_env is None
         if sp.get('native') == 'dummy':
             require_dummy_device()  # (the dim sets 6/2/2, 6/2/3 of every Gaussian kernel come with the same bit)
-        if self.dummy_env:
-            if not 1 <= eval_num <= self.HOST_EVAL_MAX:
-                raise PGMError(f'{env_name} evaluates 1..{self.HOST_EVAL_MAX} episodes per task in one launch '
-                               f'(eval_num={eval_num})')
-            if num_processes > 8:
-                raise PGMError(f'{env_name}: num_processes={num_processes} envs per task > 8 unsupported')
-            self.max_steps = int(max_steps or sp['max_episode_steps'])
-            self.bound = float(sp['bound'] if bound is None else bound)
-            self.time_limit_is_bad = True if time_limit_is_bad is None else bool(time_limit_is_bad)
-            self.R = int(envspec.DUMMY_RESETS if R is None else R)
-            if self.max_steps <= 0 or not self.bound > 0 or self.R < 1:
-                raise PGMError(f'{env_name}: max_steps={self.max_steps}, bound={self.bound} and R={self.R} must be '
-                               f'positive')
-        if self.plugin is not None:
-            if self.plugin.dims() != (self.O, self.A, self.K) or self.plugin.DISCRETE != self.discrete:
-                raise PGMError(f'env_plugin has (obs, act, obj) dims {self.plugin.dims()}, discrete = '
-                               f'{self.plugin.DISCRETE}; {env_name} is registered with {(self.O, self.A, self.K)}, '
-                               f'discrete = {self.discrete}')
-            from . import envplug
-            self.R = int(envplug.DEFAULT_RESETS if R is None else R)
-            if self.R < 1:
-                raise PGMError(f'{env_name}: R={self.R} reset-table entries per env must be at least 1')
+        self.mode = mode = (HostMode() if host_env is not None else DstMode() if self.device_env else
+                            DummyMode() if self.dummy_env else mode)
         self.act_width = 1 if self.discrete else self.A
-        self.layout = ParamLayout(self.O, self.A, self.K, self.H, layernorm=self.layernorm, discrete=self.discrete)
-        L, O, A, K, N, T = self.layout.total, self.O, self.A, self.K, self.N, self.T
         self._full = {}  # name -> full-capacity tensor whose leading dim is the task slot
-
-        def z(name, *s, dt=F32, fill=0.0):
-            t = torch.full((Pc,) + s, fill, dtype=dt, device=self.dev)
-            self._full[name] = t
-            return t
-        # spec constants + reset tables (fp64)
+        mode.setup(self, seed=seed, max_steps=max_steps, time_limit_is_bad=time_limit_is_bad, bound=bound, R=R)
+        self.layout = ParamLayout(self.O, self.A, self.K, self.H, layernorm=self.layernorm, discrete=self.discrete)
+        L, O, A, K, N, T, z = self.layout.total, self.O, self.A, self.K, self.N, self.T, self.z
+        # spec constants + reset tables (fp64); run_seeds: [num_runs][N][O], [num_runs][eval_num][O], block r run r's
         self._spec_t = {k: torch.tensor(np.ascontiguousarray(sp[k]), dtype=F64, device=self.dev)
                         for k in ('d', 'U', 'c', 'V', 'ebase', 'ecoef', 'act_lo', 'act_hi') if k in sp}
-        if self.run_seeds is None:
-            self.s0_train = torch.tensor(envspec.reset_table(O, seed, N), dtype=F64, device=self.dev)
-            self.s0_eval = torch.tensor(envspec.reset_table(O, seed, eval_num), dtype=F64, device=self.dev)
-        else:  # [num_runs][N][O] / [num_runs][eval_num][O]: block r is run r's table; every task starts in run 0
-            self.s0_train = torch.tensor(np.stack([envspec.reset_table(O, sd, N) for sd in self.run_seeds]),
-                                         dtype=F64, device=self.dev)
-            self.s0_eval = torch.tensor(np.stack([envspec.reset_table(O, sd, eval_num) for sd in self.run_seeds]),
-                                        dtype=F64, device=self.dev)
-            self.run_of_task = torch.zeros(Pc, dtype=I32, device=self.dev)
+        self.s0_train, self.s0_eval = (
+            torch.tensor(envspec.reset_table(O, seed, n) if self.run_seeds is None else
+                         np.stack([envspec.reset_table(O, sd, n) for sd in self.run_seeds]), dtype=F64, device=self.dev)
+            for n in (N, eval_num))
         # policy + optimiser: one [3][Pc][L] region
         self._state = torch.zeros(3, Pc, L, dtype=F32, device=self.dev)
         z('adam_step', dt=I32)
@@ -284,23 +626,6 @@ class TaskBatch:
         z('obj_acc', N, K, dt=F64)
         z('obj_valid', dt=I32)
         z('ret', N, dt=F64)
-        if self.dummy_env:  # per (task, env): resets since env_reset(); the reset positions [N][R][2], [eval_num][R][2]
-            z('episode', N, dt=I32)
-            self._dummy_train = torch.tensor(envspec.dummy_reset_table(seed, N, self.R), dtype=F64, device=self.dev)
-            self._dummy_eval = torch.tensor(envspec.dummy_reset_table(seed, eval_num, self.R), dtype=F64,
-                                            device=self.dev)
-        if self.plugin is not None:  # the plug-in's state words, resets since env_reset(), the reset uniforms
-            pl = self.plugin
-            z('plug_sd', N, pl.SD, dt=F64)
-            z('plug_si', N, pl.SI, dt=I32)
-            z('episode', N, dt=I32)
-            self._plug_train_np = envspec.plugin_reset_table(seed, N, self.R, pl.RW)
-            self._plug_train = torch.tensor(self._plug_train_np, dtype=F64, device=self.dev)
-            self._plug_eval = torch.tensor(envspec.plugin_reset_table(seed, eval_num, self.R, pl.RW), dtype=F64,
-                                           device=self.dev)
-            self._plug_obs0 = torch.zeros(Pc, N, O, dtype=F64, device=self.dev)
-            self._plug_par = torch.tensor(self._plug_par_np if pl.NP else [0.0], dtype=F64, device=self.dev)
-            self.env_noise = None  # [T][N][NW] fp64, allocated by the first rollout that is fed its env noise
         # rollout storage (storage.py:12-30)
         z('obs', T + 1, N, O)
         z('actions', T, N, self.act_width)
@@ -326,192 +651,50 @@ class TaskBatch:
         self.hp_task, self.lam_task = None, None  # device tables of set_task_hparams (None: the shared settings)
         self._eval_stream, self._eval_done = None, None
         self._reset_pending = False  # a pgm_ppo_update_reset queued on the side stream, not yet waited for
-        ws_bytes = lib().pgm_ppo_update_cat_workspace_bytes if self.discrete else lib().pgm_ppo_update_workspace_bytes
-        if self.any_dims:
-            ws_bytes = lib().pgm_ppo_update_any_workspace_bytes
-        nws = ws_bytes(C.byref(Dims(Pc, N, T, O, A, K, self.H, int(self.layernorm))))
+        nws = getattr(lib(), self.family.workspace_bytes)(C.byref(Dims(Pc, N, T, O, A, K, self.H, int(self.layernorm))))
         self.update_ws = torch.zeros((nws + 7) // 8, dtype=torch.int64, device=self.dev)
         # sticky OR of every update's exchange-timeout word (workspace word 2P, include/pgm_abi.h): a launch
         # whose spin-wait gave up produced invalid parameters; check_update() turns that into PGMError
         self.update_failed = torch.zeros(1, dtype=torch.int64, device=self.dev)
         self.last_fail_word = 0
-        if host_env is not None:
-            self._host_alloc(Pc)
-        if self.device_env:  # the constant raw reset observation of (row, col, step) = (0, 0, 0), for pgm_env_ingest(-1)
-            self._dst_obs0 = torch.zeros(Pc, N, O, dtype=F64, device=self.dev)
         self.set_active(P)
         self.reset_stats()
 
-    # ------------------------------------------------------------------ host-stepped environments
-    HOST_EVAL_MAX = 8  # pgm_eval_act: evaluation episodes per task in one launch
+    def __getattr__(self, name):
+        """A value its mode holds (max_steps, R, the reset tables, c_dummy, _d_act, ...) under the name it has there."""
+        try:
+            return self.__dict__['mode'].__dict__[name]
+        except KeyError:
+            raise AttributeError(f'{type(self).__name__!r} object has no attribute {name!r}') from None
 
-    def _host_alloc(self, Pc):
-        """Pinned host / device staging of the host-env mode: the sampled actions (D2H) and one packed fp64 transition
-        record per step -- raw obs | raw objectives | reward | done, bad_transition as int32 pairs -- so that a
-        step's H2D traffic is one copy."""
-        he, N, O, A, K = self.host_env, self.N, self.O, self.A, self.K
-        if tuple(he.dims()) != (O, A, K) or he.N != N:
-            raise PGMError(f'host_env has (obs, act, obj) dims {tuple(he.dims())} and {he.N} envs per task; '
-                           f'{self.env_name} with num_processes={N} needs {(O, A, K)} and {N}')
-        if getattr(he, 'capacity', he.P) < Pc:
-            raise PGMError(f'host_env holds {getattr(he, "capacity", he.P)} tasks, the batch needs {Pc}')
-        if self.eval_num > self.HOST_EVAL_MAX:
-            raise PGMError(f'host-env mode evaluates at most {self.HOST_EVAL_MAX} episodes per task '
-                           f'(eval_num={self.eval_num})')
-        if bool(getattr(he, 'discrete', False)) != self.discrete:
-            raise PGMError(f'host_env.discrete = {getattr(he, "discrete", False)} but {self.env_name} has '
-                           f'{"discrete" if self.discrete else "continuous"} actions')
-        E = self.eval_num
-        if self.discrete:  # one int32 action index per env / evaluation episode
-            self._h_act = torch.empty(Pc, N, dtype=I32, pin_memory=True)
-            self._d_act = torch.zeros(Pc, N, dtype=I32, device=self.dev)
-            A, adt = 1, I32
-        else:
-            self._h_act = torch.empty(Pc, N, A, dtype=F32, pin_memory=True)
-            self._d_act = torch.zeros(Pc, N, A, dtype=F32, device=self.dev)
-            adt = F32
-        n = Pc * N * (O + K + 2)
-        self._h_tr = torch.zeros(n, dtype=F64, pin_memory=True)
-        self._d_tr = torch.zeros(n, dtype=F64, device=self.dev)
-        self._tr_ready = None  # the last H2D copy out of _h_tr (the host waits for it before rewriting the buffer)
-        self._h_eobs = torch.zeros(Pc * E * O, dtype=F64, pin_memory=True)
-        self._d_eobs = torch.zeros(Pc * E * O, dtype=F64, device=self.dev)
-        self._h_eact = torch.empty(Pc * E * A, dtype=adt, pin_memory=True)
-        self._d_eact = torch.zeros(Pc * E * A, dtype=adt, device=self.dev)
+    def z(self, name, *s, dt=F32, fill=0.0):
+        """A per-task tensor [capacity, *s]; set_active re-slices its active slots into the attribute ``name``."""
+        t = torch.full((self.capacity,) + s, fill, dtype=dt, device=self.dev)
+        self._full[name] = t
+        return t
 
-    def _host_views(self):
-        P, N, O, K = self.P, self.N, self.O, self.K
-        n1, n2, n3 = P * N * O, P * N * K, P * N
+    # ------------------------------------------------------------------ the family's kernels
+    def _launch(self, name, dims, *args):
+        """Entry point `name` of the batch's kernel family: (dims, [head,] args..., stream)."""
+        _call(name, C.byref(dims), *((int(self.discrete),) if self.family.head else ()), *args)
 
-        def seg(buf):
-            flags = buf[n1 + n2 + n3:n1 + n2 + 2 * n3].view(I32).view(2, P, N)
-            return (buf[:n1].view(P, N, O), buf[n1:n1 + n2].view(P, N, K), buf[n1 + n2:n1 + n2 + n3].view(P, N),
-                    flags[0], flags[1])
-        self._tr_len = n1 + n2 + 2 * n3
-        self._d_seg = seg(self._d_tr)
-        self._h_seg = tuple(v.numpy() for v in seg(self._h_tr))
-        self.host_env.set_active(P)
+    def _env_ingest(self, t, obs, obj=None, rew=None, done=None, bad=None):
+        """env_ingest(t) on device buffers: VecNormalize + insert into slot t + 1 (t = -1: the reset observation)."""
+        _call(self.family.env_ingest, C.byref(self.dims), C.byref(self.c_state), C.byref(self.c_norm),
+              C.byref(self.c_rb), t, _ptr(obs), _ptr(obj), _ptr(rew), _ptr(done), _ptr(bad))
 
     def _ingest(self, t, obs, rew=None, done=None, bad=None, obj=None):
-        """One packed H2D copy of the host transition, then pgm_env_ingest(t) (t = -1: the reset observation)."""
-        if self._tr_ready is not None:
-            self._tr_ready.synchronize()
-        ho, hj, hr, hd, hb = self._h_seg
-        ho[...] = obs
-        if t >= 0:
-            hj[...], hr[...], hd[...], hb[...] = obj, rew, done, bad
-        n = self._tr_len
-        self._d_tr[:n].copy_(self._h_tr[:n], non_blocking=True)
-        self._tr_ready = torch.cuda.Event()
-        self._tr_ready.record()
-        do, dj, dr, dd, db = self._d_seg
-        if self.any_dims:
-            check(lib().pgm_env_ingest_any(C.byref(self.dims), C.byref(self.c_state), C.byref(self.c_norm),
-                                           C.byref(self.c_rb), t, _ptr(do), _ptr(dj), _ptr(dr), _ptr(dd), _ptr(db),
-                                           _stream()), 'pgm_env_ingest_any')
-            return
-        check(lib().pgm_env_ingest(C.byref(self.dims), C.byref(self.c_state), C.byref(self.c_norm),
-                                   C.byref(self.c_rb), t, _ptr(do), _ptr(dj), _ptr(dr), _ptr(dd), _ptr(db),
-                                   _stream()), 'pgm_env_ingest')
+        """One packed H2D copy of the host transition, then env_ingest(t) (t = -1: the reset observation)."""
+        self._env_ingest(t, *self.mode.stage(t, obs, rew, done, bad, obj))
 
     def _draw_noise(self, seed):
         """The perf-mode counter stream of `seed` into self.noise: normals, or (discrete) uniforms."""
-        fn, what = ((lib().pgm_uniform_noise, 'pgm_uniform_noise') if self.discrete
-                    else (lib().pgm_normal_noise, 'pgm_normal_noise'))
-        check(fn(self.noise.numel(), C.c_uint64(seed), _ptr(self.noise), _stream()), what)
+        _call('pgm_uniform_noise' if self.discrete else 'pgm_normal_noise', self.noise.numel(), C.c_uint64(seed),
+              _ptr(self.noise))
 
     def _rollout_act(self, t):
-        if self.any_dims:
-            check(lib().pgm_rollout_act_any(C.byref(self.dims), int(self.discrete), _ptr(self.params),
-                                            C.byref(self.c_rb), t, _ptr(self.noise), _ptr(self._d_act), _stream()),
-                  'pgm_rollout_act_any')
-            return
-        if self.discrete:
-            check(lib().pgm_rollout_act_cat(C.byref(self.dims), _ptr(self.params), C.byref(self.c_rb), t,
-                                            _ptr(self.noise), _ptr(self._d_act), _stream()), 'pgm_rollout_act_cat')
-            return
-        check(lib().pgm_rollout_act(C.byref(self.dims), _ptr(self.params), C.byref(self.c_rb), t, _ptr(self.noise),
-                                    _ptr(self._d_act), _stream()), 'pgm_rollout_act')
-
-    def _host_rollout(self, seed, noise, carry, env_noise=None):
-        """morl/mopg.py:103-135 with the env on the host: per step t the device acts on obs[t], the actions go to the
-        host (pinned D2H + the step's one stream synchronise), the host envs step, the transition returns (pinned
-        H2D) and the device applies VecNormalize + insert into slot t + 1; then the bootstrap value."""
-        import time
-        P, T = self.P, self.T
-        if hasattr(self.host_env, 'begin_rollout'):  # a host-stepped contract-2 plug-in: this rollout's env noise
-            from . import envplug
-            self.host_env.begin_rollout(envplug.env_seed(seed), None if env_noise is None else
-                                        torch.as_tensor(env_noise).detach().cpu().numpy())
-        elif env_noise is not None:
-            raise PGMError('rollout(env_noise=...): only a contract-2 env plug-in with NW > 0 takes env noise')
-        if noise is None:  # the perf-mode counter stream of `seed`: what the fused rollout draws in-kernel
-            self._draw_noise(seed)
-        elif noise is not self.noise:
-            self.noise.copy_(noise.to(dtype=F32))
-        if carry:  # after_update(): slot T -> slot 0 (storage.py:71-75)
-            self.obs[:, 0].copy_(self.obs[:, T])
-            self.masks[:, 0].copy_(self.masks[:, T])
-            self.bad_masks[:, 0].copy_(self.bad_masks[:, T])
-        stream = torch.cuda.current_stream()
-        prof = self.host_profile
-        h_act = self._h_act[:P]
-        a_np = h_act.numpy()
-        for t in range(T):
-            t0 = time.perf_counter()
-            self._rollout_act(t)
-            h_act.copy_(self._d_act[:P], non_blocking=True)
-            stream.synchronize()
-            t1 = time.perf_counter()
-            obs, rew, done, bad, obj = self.host_env.step(a_np)
-            t2 = time.perf_counter()
-            self._ingest(t, obs, rew, done, bad, obj)
-            if prof is not None:
-                stream.synchronize()  # (only when timed: the ingest otherwise overlaps nothing the host waits for)
-                prof['act'] += t1 - t0
-                prof['step'] += t2 - t1
-                prof['ingest'] += time.perf_counter() - t2
-        self._rollout_act(T)
-
-    def _host_evaluate(self, mean, var, out):
-        """evaluation() (morl/mopg.py:25-46) with the episodes on the host: eval_num episodes per task step together,
-        pgm_eval_act normalises with the frozen statistics and returns the deterministic actions; an ended episode
-        stops contributing."""
-        P, E, O, A, K = self.P, self.eval_num, self.O, self.A, self.K
-        he = self.host_env
-        stream = torch.cuda.current_stream()
-        h_obs = self._h_eobs[:P * E * O]
-        if self.discrete:  # int32 action indices [P, E] from pgm_eval_act_cat
-            A = 1
-            eval_act, what, ashape = lib().pgm_eval_act_cat, 'pgm_eval_act_cat', (P, E)
-        else:
-            eval_act, what, ashape = lib().pgm_eval_act, 'pgm_eval_act', (P, E, A)
-        h_act = self._h_eact[:P * E * A]
-        obs_np, act_np = h_obs.numpy().reshape(P, E, O), h_act.numpy().reshape(ashape)
-        acc = np.zeros((P, E, K))
-        disc = 1.0
-        alive = np.ones((P, E), dtype=bool)
-        obs = he.eval_reset(E)
-        d = Dims(P, 1, 0, O, self.A, K, self.H, int(self.layernorm))
-        if self.any_dims:
-            any_fn, head, what = lib().pgm_eval_act_any, int(self.discrete), 'pgm_eval_act_any'
-
-            def eval_act(d_, *rest):
-                return any_fn(d_, head, *rest)
-        while alive.any():
-            obs_np[...] = obs
-            self._d_eobs[:P * E * O].copy_(h_obs, non_blocking=True)
-            check(eval_act(C.byref(d), _ptr(self.params), _ptr(mean), _ptr(var), int(self.use_ob_rms),
-                           _ptr(self._d_eobs), E, _ptr(self._d_eact), _stream()), what)
-            h_act.copy_(self._d_eact[:P * E * A], non_blocking=True)
-            stream.synchronize()
-            obs, obj, done = he.eval_step(act_np)
-            acc += np.where(alive[..., None], disc * np.asarray(obj, dtype=np.float64), 0.0)
-            if not self.raw:
-                disc *= self.gamma
-            alive &= ~np.asarray(done, dtype=bool)
-        out.copy_(torch.from_numpy(acc.sum(1) / E))
-        return out
+        self._launch(self.family.rollout_act, self.dims, _ptr(self.params), C.byref(self.c_rb), t, _ptr(self.noise),
+                     _ptr(self.mode._d_act))
 
     def set_active(self, P):
         """Run the first P task slots (P <= capacity): re-slices the public views and the kernels' dims."""
@@ -528,8 +711,7 @@ class TaskBatch:
                 self._ob_src = self._stats64[off:off + 2 * self.capacity * w].view(2, self.capacity, w)
         self._eval_mean, self._eval_var = self._eval_ob[0, :P], self._eval_ob[1, :P]
         self._build_structs()
-        if self.host_env is not None:
-            self._host_views()
+        self.mode.views(self)
 
     def set_runs(self, ids):
         """run_of_task of the active tasks: ids[p] in [0, len(run_seeds)) is the run whose reset tables task p uses.
@@ -551,8 +733,7 @@ class TaskBatch:
         gae() and ppo_update_launch() go through pgm_gae_tasks / pgm_ppo_update_tasks.  A batch that never calls this
         launches what it always launched.  Plain and LayerNorm Gaussian batches on the SynthMO device envs only."""
         for flag, on in (('discrete actions', self.discrete), ('any_dims', self.any_dims),
-                         ('env_plugin', self.plugin is not None), ('device_env', self.device_env),
-                         ('an MO-Dummy env', self.dummy_env), ('host_env', self.host_env is not None)):
+                         (self.mode.name, self.mode.name is not None)):
             if on:
                 raise PGMError(f'set_task_hparams: per-task PPO settings exist for the update kernels of '
                                f'pgm_ppo_update on the SynthMO device envs only; this batch has {flag}')
@@ -637,11 +818,6 @@ class TaskBatch:
                                 int(self.use_obj_rms))
         self.c_rb = RolloutBuf(*(_ptr(t) for t in (self.obs, self.actions, self.logp, self.values, self.rewards,
                                                    self.masks, self.bad_masks, self.returns, self.adv)))
-        if self.dummy_env:
-            tlb = int(self.time_limit_is_bad)
-            self.c_dummy = DummySpec(self.max_steps, tlb, self.bound, _ptr(self._dummy_train), self.R, self.N)
-            self.c_dummy_eval = DummySpec(self.max_steps, tlb, self.bound, _ptr(self._dummy_eval), self.R,
-                                          self.eval_num)
 
     def reset_stats(self):
         """Fresh RunningMeanStd objects: count 1e-4, mean 0, var 1 (running_mean_std.py:5-8)."""
@@ -654,77 +830,19 @@ class TaskBatch:
     # ------------------------------------------------------------------ kernels
     def env_reset(self):
         """Fresh make_vec_envs + envs.reset() (mopg.py:67-82): obs[:, 0], masks[:, 0] = 1."""
-        if self.host_env is not None:  # one H2D copy of the host envs' reset observations, then the ingest kernel
-            self._ingest(-1, self.host_env.reset())
-            return self.obs[:, 0]
-        if self.device_env:  # every env at (0, 0, 0); VecNormalize.reset on the constant reset observation
-            self.s.zero_()
-            check(lib().pgm_env_ingest(C.byref(self.dims), C.byref(self.c_state), C.byref(self.c_norm),
-                                       C.byref(self.c_rb), -1, _ptr(self._dst_obs0), None, None, None, None,
-                                       _stream()), 'pgm_env_ingest')
-            return self.obs[:, 0]
-        if self.plugin is not None:  # env n of every task at entry (n, 0) of its row: the header's reset on the host
-            P, N, pl = self.P, self.N, self.plugin
-            row = np.broadcast_to(np.arange(N, dtype=np.int32), (P, N)).reshape(-1)
-            sd, si, obs = pl.reset(row, np.zeros(P * N, dtype=np.int32), self._plug_train_np, par=self._plug_par_np)
-            self.plug_sd.copy_(torch.from_numpy(sd.reshape(P, N, pl.SD)))
-            self.plug_si.copy_(torch.from_numpy(si.reshape(P, N, pl.SI)))
-            self._plug_obs0[:P].copy_(torch.from_numpy(obs.reshape(P, N, self.O)))
-            self.elapsed.zero_()
-            self.episode.zero_()
-            check(lib().pgm_env_ingest_any(C.byref(self.dims), C.byref(self.c_state), C.byref(self.c_norm),
-                                           C.byref(self.c_rb), -1, _ptr(self._plug_obs0), None, None, None, None,
-                                           _stream()), 'pgm_env_ingest_any')
-            return self.obs[:, 0]
-        if self.dummy_env:  # env n of every task at entry (n, 0) of the reset table, at rest; VecNormalize.reset
-            self.s.zero_()
-            self.s[:, :, :2] = self._dummy_train[:, 0]
-            self.elapsed.zero_()
-            self.episode.zero_()
-            check(lib().pgm_env_ingest(C.byref(self.dims), C.byref(self.c_state), C.byref(self.c_norm),
-                                       C.byref(self.c_rb), -1, _ptr(self.s), None, None, None, None, _stream()),
-                  'pgm_env_ingest')
-            return self.obs[:, 0]
-        out = torch.empty(self.P, self.N, self.O, dtype=F32, device=self.dev)
-        if self.run_seeds is not None:
-            check(lib().pgm_env_reset_runs(C.byref(self.dims), C.byref(self.c_spec), C.byref(self.c_state),
-                                           C.byref(self.c_norm), _ptr(self.run_of_task), len(self.run_seeds),
-                                           _ptr(out), _stream()), 'pgm_env_reset_runs')
-        else:
-            check(lib().pgm_env_reset(C.byref(self.dims), C.byref(self.c_spec), C.byref(self.c_state),
-                                      C.byref(self.c_norm), _ptr(out), _stream()), 'pgm_env_reset')
-        self.obs[:, 0].copy_(out)
-        self.masks[:, 0] = 1.0
-        self.bad_masks[:, 0] = 1.0
-        return out
+        out = self.mode.reset(self)
+        return self.obs[:, 0] if out is None else out
 
     def env_step(self, action):
-        if self.plugin is not None:
-            raise PGMError('env_step: an env plug-in is stepped inside pgm_envplug_rollout / pgm_envplug_eval; there '
-                           'is no single-step kernel (EnvPlugin.transition evaluates the header on the host)')
-        if self.any_dims:
-            raise PGMError('env_step: this batch runs on the runtime-dim kernels, which are host-stepped only: the '
-                           'environments are stepped inside rollout(), there is no device env to step')
-        if self.run_seeds is not None:
-            raise PGMError('env_step: a multi-run batch (run_seeds=...) has no single-step kernel that takes the reset '
-                           'rows per task; the envs are stepped inside rollout()')
-        if self.host_env is not None:
-            raise PGMError('env_step: this batch is in host-env mode (TaskBatch(host_env=...)): the environments are '
-                           'stepped on the host inside rollout(), there is no device env to step')
-        if self.device_env:
-            raise PGMError('env_step: the device Deep Sea Treasure is stepped inside pgm_rollout_dst / pgm_eval_dst; '
-                           'there is no single-step kernel (pgm_dst_transition evaluates the rule on the host)')
-        if self.dummy_env:
-            raise PGMError(f'env_step: {self.env_name} is stepped inside pgm_rollout_dummy / pgm_eval_dummy; there is '
-                           f'no single-step kernel (pgm_dummy_transition evaluates the rule on the host)')
+        if self.mode.no_step is not None:
+            raise PGMError(self.mode.no_step)
         P, N, O, K = self.P, self.N, self.O, self.K
         action = action.to(device=self.dev, dtype=F32).contiguous()
         obs = torch.empty(P, N, O, dtype=F32, device=self.dev)
         rew = torch.empty(P, N, K, dtype=F32, device=self.dev)
         m, b = torch.empty(P, N, dtype=F32, device=self.dev), torch.empty(P, N, dtype=F32, device=self.dev)
-        check(lib().pgm_env_step(C.byref(self.dims), C.byref(self.c_spec), C.byref(self.c_state),
-                                 C.byref(self.c_norm), _ptr(action), _ptr(obs), _ptr(rew), _ptr(m), _ptr(b),
-                                 _stream()), 'pgm_env_step')
+        _call('pgm_env_step', C.byref(self.dims), C.byref(self.c_spec), C.byref(self.c_state), C.byref(self.c_norm),
+              _ptr(action), _ptr(obs), _ptr(rew), _ptr(m), _ptr(b))
         return obs, rew, m, b
 
     def act(self, obs, noise=None, deterministic=False):
@@ -737,93 +855,30 @@ class TaskBatch:
         value = torch.empty(P, N, self.K, dtype=F32, device=self.dev)
         logp = torch.empty(P, N, dtype=F32, device=self.dev)
         nz = None if noise is None else noise.to(device=self.dev, dtype=F32).contiguous()
-        if self.discrete:  # noise: uniforms [N]; the action is the int32 index [P, N]
-            action = torch.empty(P, N, dtype=I32, device=self.dev)
-            check(lib().pgm_act_forward_cat(C.byref(d), _ptr(self.params), _ptr(obs), _ptr(nz), int(deterministic),
-                                            _ptr(value), _ptr(action), _ptr(logp), _stream()), 'pgm_act_forward_cat')
-            return value, action, logp
-        action = torch.empty(P, N, self.A, dtype=F32, device=self.dev)
-        check(lib().pgm_act_forward(C.byref(d), _ptr(self.params), _ptr(obs), _ptr(nz), int(deterministic),
-                                    _ptr(value), _ptr(action), _ptr(logp), _stream()), 'pgm_act_forward')
+        # discrete: noise is uniforms [N], the action the int32 index [P, N]
+        action = torch.empty((P, N) if self.discrete else (P, N, self.A), dtype=I32 if self.discrete else F32,
+                             device=self.dev)
+        _call('pgm_act_forward_cat' if self.discrete else 'pgm_act_forward', C.byref(d), _ptr(self.params), _ptr(obs),
+              _ptr(nz), int(deterministic), _ptr(value), _ptr(action), _ptr(logp))
         return value, action, logp
 
     def rollout(self, seed, noise=None, carry=True, env_noise=None):
-        """env_noise (a contract-2 plug-in with NW > 0, fused or host-stepped): the steps' uniforms [T][N][NW] in
+        """noise: the steps' action noise (normals [T][N][A] / uniforms [T][N]); None: the counter stream of `seed`.
+        env_noise (a contract-2 plug-in with NW > 0, fused or host-stepped): the steps' uniforms [T][N][NW] in
         [0, 1); None draws the stream of envplug.env_seed(seed)."""
-        if self.host_env is not None:
-            return self._host_rollout(seed, noise, carry, env_noise)
-        if env_noise is not None and (self.plugin is None or self.plugin.NW == 0):
-            raise PGMError('rollout(env_noise=...): only a contract-2 env plug-in with NW > 0 takes env noise')
-        nz = None
-        if noise is not None:
-            if noise is not self.noise:
-                self.noise.copy_(noise.to(dtype=F32))
-            nz = self.noise
-        if self.plugin is not None:  # noise: normals [T][N][A] / uniforms [T][N]; None: the counter stream of `seed`
-            pl = self.plugin
-            if pl.CONTRACT == 1:
-                pl.check(pl.h.pgm_envplug_rollout(C.byref(self.dims), _ptr(self.params), _ptr(self.plug_sd),
-                                                  _ptr(self.plug_si), _ptr(self.episode), _ptr(self._plug_train),
-                                                  self.R, self.N, C.byref(self.c_state), C.byref(self.c_norm),
-                                                  C.byref(self.c_rb), _ptr(nz), C.c_uint64(seed), int(carry),
-                                                  _stream()), 'pgm_envplug_rollout')
-                return
-            from . import envplug
-            ez = None
-            if env_noise is not None:
-                shape = (self.T, self.N, pl.NW)
-                if tuple(env_noise.shape) != shape:
-                    raise PGMError(f'rollout(env_noise=...) of shape {tuple(env_noise.shape)}: this batch steps '
-                                   f'[T][N][NW] = {shape}')
-                if self.env_noise is None:
-                    self.env_noise = torch.zeros(shape, dtype=F64, device=self.dev)
-                self.env_noise.copy_(torch.as_tensor(env_noise).to(dtype=F64))
-                ez = self.env_noise
-            pl.check(pl.h.pgm_envplug_rollout_ex(C.byref(self.dims), _ptr(self.params), _ptr(self.plug_sd),
-                                                 _ptr(self.plug_si), _ptr(self.episode), _ptr(self._plug_train),
-                                                 self.R, self.N, C.byref(self.c_state), C.byref(self.c_norm),
-                                                 C.byref(self.c_rb), _ptr(nz), C.c_uint64(seed), int(carry),
-                                                 _ptr(self._plug_par), _ptr(ez),
-                                                 C.c_uint64(envplug.env_seed(seed)), _stream()),
-                     'pgm_envplug_rollout_ex')
-            return
-        if self.device_env:  # noise: uniforms [T][N]; None: the kernel draws pgm_uniform_noise's stream of `seed`
-            check(lib().pgm_rollout_dst(C.byref(self.dims), _ptr(self.params), C.byref(self.c_dst),
-                                        C.byref(self.c_state), C.byref(self.c_norm), C.byref(self.c_rb), _ptr(nz),
-                                        C.c_uint64(seed), int(carry), _stream()), 'pgm_rollout_dst')
-            return
-        if self.dummy_env:  # noise: normals [T][N][A]; None: the kernel draws pgm_normal_noise's stream of `seed`
-            check(lib().pgm_rollout_dummy(C.byref(self.dims), _ptr(self.params), C.byref(self.c_dummy),
-                                          C.byref(self.c_state), _ptr(self.episode), C.byref(self.c_norm),
-                                          C.byref(self.c_rb), _ptr(nz), C.c_uint64(seed), int(carry), _stream()),
-                  'pgm_rollout_dummy')
-            return
-        if self.run_seeds is not None:
-            check(lib().pgm_rollout_runs(C.byref(self.dims), _ptr(self.params), C.byref(self.c_spec),
-                                         C.byref(self.c_state), C.byref(self.c_norm), C.byref(self.c_rb), _ptr(nz),
-                                         C.c_uint64(seed), int(carry), _ptr(self.run_of_task), len(self.run_seeds),
-                                         C.byref(launch_opts()), _stream()), 'pgm_rollout_runs')
-            return
-        check(lib().pgm_rollout(C.byref(self.dims), _ptr(self.params), C.byref(self.c_spec), C.byref(self.c_state),
-                                C.byref(self.c_norm), C.byref(self.c_rb), _ptr(nz), C.c_uint64(seed),
-                                int(carry), C.byref(launch_opts()), _stream()), 'pgm_rollout')
+        self.mode.rollout(self, seed, noise, carry, env_noise)
 
     def gae(self):
-        if self.lam_task is not None:
-            check(lib().pgm_gae_tasks(C.byref(self.dims), C.byref(self.c_rb), self.gamma, _ptr(self.lam_task),
-                                      int(self.use_gae), int(self.proper), _stream()), 'pgm_gae_tasks')
-            return
-        check(lib().pgm_gae(C.byref(self.dims), C.byref(self.c_rb), self.gamma, self.gae_lambda, int(self.use_gae),
-                            int(self.proper), _stream()), 'pgm_gae')
+        name, lam = ('pgm_gae', self.gae_lambda) if self.lam_task is None else ('pgm_gae_tasks', _ptr(self.lam_task))
+        _call(name, C.byref(self.dims), C.byref(self.c_rb), self.gamma, lam, int(self.use_gae), int(self.proper))
 
     def adv_normalize(self):
         var = self.obj_var if self.use_obj_rms else None
-        check(lib().pgm_adv_normalize(C.byref(self.dims), C.byref(self.c_rb), _ptr(self.weights), _ptr(var),
-                                      _stream()), 'pgm_adv_normalize')
+        _call('pgm_adv_normalize', C.byref(self.dims), C.byref(self.c_rb), _ptr(self.weights), _ptr(var))
 
     def make_perms(self, seed):
         E, n = self.perms.shape
-        check(lib().pgm_randperm(n, E, C.c_uint64(seed), _ptr(self.perms), _stream()), 'pgm_randperm')
+        _call('pgm_randperm', n, E, C.c_uint64(seed), _ptr(self.perms))
 
     def ppo_update(self, perms=None, defer_flag=False):
         """The update on the current stream.  The exchange-timeout word of this launch is OR-ed into the sticky
@@ -842,38 +897,19 @@ class TaskBatch:
         torch.bitwise_or(self.update_failed, flag, out=self.update_failed)  # stream-ordered, no host sync
 
     def ppo_update_launch(self):
-        """pgm_ppo_update alone (packed rows + the update kernel) on the current stream; discrete actions:
-        pgm_ppo_update_cat (it gathers from the storage itself: no packed rows)."""
-        if self.any_dims:
-            check(lib().pgm_ppo_update_any(C.byref(self.dims), int(self.discrete), C.byref(self.hp), _ptr(self.params),
-                                           _ptr(self.adam_m), _ptr(self.adam_v), _ptr(self.adam_step), _ptr(self.lr),
-                                           _ptr(self.perms), C.byref(self.c_rb), _ptr(self.stats),
-                                           _ptr(self.update_ws), _stream()), 'pgm_ppo_update_any')
-            return
-        if self.discrete:
-            check(lib().pgm_ppo_update_cat(C.byref(self.dims), C.byref(self.hp), _ptr(self.params), _ptr(self.adam_m),
-                                           _ptr(self.adam_v), _ptr(self.adam_step), _ptr(self.lr), _ptr(self.perms),
-                                           C.byref(self.c_rb), _ptr(self.stats), _ptr(self.update_ws), _stream()),
-                  'pgm_ppo_update_cat')
-            return
-        if self.hp_task is not None:
-            check(lib().pgm_ppo_update_tasks(C.byref(self.dims), C.byref(self.hp), _ptr(self.hp_task),
-                                             _ptr(self.params), _ptr(self.adam_m), _ptr(self.adam_v),
-                                             _ptr(self.adam_step), _ptr(self.lr), _ptr(self.perms), C.byref(self.c_rb),
-                                             _ptr(self.stats), _ptr(self.update_ws), C.byref(launch_opts()),
-                                             _stream()), 'pgm_ppo_update_tasks')
-            return
-        check(lib().pgm_ppo_update(C.byref(self.dims), C.byref(self.hp), _ptr(self.params), _ptr(self.adam_m),
-                                   _ptr(self.adam_v), _ptr(self.adam_step), _ptr(self.lr), _ptr(self.perms),
-                                   C.byref(self.c_rb), _ptr(self.stats), _ptr(self.update_ws),
-                                   C.byref(launch_opts()), _stream()), 'pgm_ppo_update')
+        """The family's update alone on the current stream (pgm_ppo_update: packed rows + the update kernel; the
+        others gather from the storage themselves); after set_task_hparams, pgm_ppo_update_tasks."""
+        fam, name, hp = self.family, self.family.ppo_update, (C.byref(self.hp),)
+        if fam.tasks and self.hp_task is not None:
+            name, hp = name + '_tasks', hp + (_ptr(self.hp_task),)
+        self._launch(name, self.dims, *hp, _ptr(self.params), _ptr(self.adam_m), _ptr(self.adam_v),
+                     _ptr(self.adam_step), _ptr(self.lr), _ptr(self.perms), C.byref(self.c_rb), _ptr(self.stats),
+                     _ptr(self.update_ws), *((C.byref(launch_opts()),) if fam.opts else ()))
 
     def update_variant(self):
         """The update kernel pgm_ppo_update launches for this batch (pgm_ppo_update_variant: the launcher's own rule)."""
-        if self.any_dims:
-            return 'ppo_update_any_kernel'
-        if self.discrete:  # one kernel, no launch choice
-            return 'ppo_update_cat_kernel (one workgroup per tower)'
+        if self.family.variant is not None:  # one kernel, no launch choice
+            return self.family.variant
         buf = C.create_string_buffer(128)
         check(lib().pgm_ppo_update_variant(C.byref(self.dims), C.byref(self.hp), C.byref(launch_opts()), buf, 128),
               'pgm_ppo_update_variant')
@@ -901,41 +937,7 @@ class TaskBatch:
         mean = self.ob_mean if ob_mean is None else ob_mean
         var = self.ob_var if ob_var is None else ob_var
         out = self.objs if out is None else out
-        if self.host_env is not None:
-            return self._host_evaluate(mean, var, out)
-        if self.plugin is not None:
-            pl = self.plugin
-            if pl.CONTRACT == 1:
-                pl.check(pl.h.pgm_envplug_eval(C.byref(self.dims), _ptr(self.params), _ptr(self._plug_eval), self.R,
-                                               self.eval_num, _ptr(mean), _ptr(var), self.eval_num,
-                                               int(self.use_ob_rms), int(self.raw), self.gamma, _ptr(out), _stream()),
-                         'pgm_envplug_eval')
-                return out
-            pl.check(pl.h.pgm_envplug_eval_ex(C.byref(self.dims), _ptr(self.params), _ptr(self._plug_eval), self.R,
-                                              self.eval_num, _ptr(mean), _ptr(var), self.eval_num,
-                                              int(self.use_ob_rms), int(self.raw), self.gamma, _ptr(out),
-                                              _ptr(self._plug_par), C.c_uint64(self._plug_eval_seed), _stream()),
-                     'pgm_envplug_eval_ex')
-            return out
-        if self.device_env:
-            check(lib().pgm_eval_dst(C.byref(self.dims), _ptr(self.params), C.byref(self.c_dst), _ptr(mean), _ptr(var),
-                                     self.eval_num, int(self.use_ob_rms), int(self.raw), self.gamma, _ptr(out),
-                                     _stream()), 'pgm_eval_dst')
-            return out
-        if self.dummy_env:
-            check(lib().pgm_eval_dummy(C.byref(self.dims), _ptr(self.params), C.byref(self.c_dummy_eval), _ptr(mean),
-                                       _ptr(var), self.eval_num, int(self.use_ob_rms), int(self.raw), self.gamma,
-                                       _ptr(out), _stream()), 'pgm_eval_dummy')
-            return out
-        if self.run_seeds is not None:
-            check(lib().pgm_eval_runs(C.byref(self.dims), _ptr(self.params), C.byref(self.c_spec), _ptr(mean),
-                                      _ptr(var), _ptr(self.s0_eval), self.eval_num, int(self.use_ob_rms),
-                                      int(self.raw), self.gamma, _ptr(out), _ptr(self.run_of_task),
-                                      len(self.run_seeds), C.byref(launch_opts()), _stream()), 'pgm_eval_runs')
-            return out
-        check(lib().pgm_eval(C.byref(self.dims), _ptr(self.params), C.byref(self.c_spec), _ptr(mean), _ptr(var),
-                             _ptr(self.s0_eval), self.eval_num, int(self.use_ob_rms), int(self.raw), self.gamma,
-                             _ptr(out), C.byref(launch_opts()), _stream()), 'pgm_eval')
+        self.mode.evaluate(self, mean, var, out)
         return out
 
     @property
@@ -963,14 +965,12 @@ class TaskBatch:
         this iteration's ob_rms (the next rollout advances the live one) and writes objs_out (default
         self.objs), readable after wait_eval() or from work queued on eval_stream.
 
-        Host-env mode: the evaluation is a host episode loop that synchronises every step, so there is nothing to
-        overlap: overlap_eval is ignored and the evaluation simply runs after the update, with the live ob_rms
-        (which the next rollout has not advanced yet)."""
-        if self.host_env is not None:
-            overlap_eval = False
-        # perf mode: the counter stream of iteration j, drawn by one wide kernel up front (the fused Deep Sea Treasure
-        # and MO-Dummy rollouts draw the same stream inside the kernel: noise stays None)
-        if noise is None and not self.device_env and not self.dummy_env and self.plugin is None:
+        A mode whose evaluation cannot overlap (HostMode: a host episode loop that synchronises every step) ignores
+        overlap_eval: the evaluation runs after the update, with the live ob_rms (not yet advanced by a rollout)."""
+        overlap_eval = overlap_eval and self.mode.overlap
+        # perf mode: the counter stream of iteration j, drawn by one wide kernel up front (a mode with fused_noise
+        # draws the same stream inside its rollout kernel: noise stays None)
+        if noise is None and not self.mode.fused_noise:
             self._draw_noise(j)
             noise = self.noise
         perm_ready = None
@@ -1013,10 +1013,9 @@ class TaskBatch:
             # the timeout word of this update, folded off the main stream, then the next update's workspace reset
             # (the next update waits for this stream: perm_ready)
             self.fold_update_flag()
-            if not self.discrete and not self.any_dims:  # (pgm_ppo_update_cat / _any reset their own, smaller workspace:
-                # pgm_ppo_update_reset clears the exchange slots of pgm_ppo_update's layout, which it does not have)
-                check(lib().pgm_ppo_update_reset(C.byref(self.dims), _ptr(self.update_ws), _stream()),
-                      'pgm_ppo_update_reset')
+            if self.family.opts:  # (the other families reset their own, smaller workspace: pgm_ppo_update_reset clears
+                # the exchange slots of pgm_ppo_update's layout, which they do not have)
+                _call('pgm_ppo_update_reset', C.byref(self.dims), _ptr(self.update_ws))
                 self._reset_pending = True
             out = self.evaluate(self._eval_mean, self._eval_var, out=objs_out)
             out.record_stream(side)

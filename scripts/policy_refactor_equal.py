@@ -122,7 +122,8 @@ def collect_seam(out):
             tb.noise.copy_(torch.rand(T, N, generator=g) if tb.discrete else torch.randn(T, N, tb.A, generator=g))
             for t in (0, T - 1, T):
                 tb._rollout_act(t)
-                _snap(out, f'{tag}/act{t}', tb, ('values', 'actions', 'logp', '_d_act'))
+                _snap(out, f'{tag}/act{t}', tb, ('values', 'actions', 'logp'))
+                _snap(out, f'{tag}/act{t}', tb.mode, ('_d_act',))
             done = rng.rand(P, N) < 0.4
             tb._ingest(0, rng.randn(P, N, O), rng.randn(P, N), done, done & (rng.rand(P, N) < 0.5), rng.randn(P, N, K))
             _snap(out, f'{tag}/ingest0', tb, ('obs', 'rewards', 'masks', 'bad_masks', 'obj_acc', 'obj_valid', 'ret',

@@ -342,14 +342,14 @@ def test_taskbatch_defaults_and_refusals():
     from pgmorl_amd.runtime import TaskBatch
     tb = TaskBatch('MO-Dummy3-v0', 2, num_processes=3, num_steps=8, device='cpu', seed=3, eval_num=2)
     assert tb.dummy_env and not tb.device_env and not tb.discrete and tb.host_env is None and (tb.O, tb.A, tb.K) == (6, 2, 3)
-    assert (tb.max_steps, tb.bound, tb.time_limit_is_bad, tb.R) == (500, 5.0, True, 256)
+    assert (tb.mode.max_steps, tb.mode.bound, tb.mode.time_limit_is_bad, tb.mode.R) == (500, 5.0, True, 256)
     assert tb.episode.shape == (2, 3) and tb.episode.dtype == torch.int32 and tb.noise.shape == (8, 3, 2)
-    assert np.array_equal(tb._dummy_train.numpy(), envspec.dummy_reset_table(3, 3))
-    assert np.array_equal(tb._dummy_eval.numpy(), envspec.dummy_reset_table(3, 2))
-    assert tb.c_dummy.reset_count == 3 and tb.c_dummy_eval.reset_count == 2 and tb.c_dummy.time_limit_is_bad == 1
+    assert np.array_equal(tb.mode._dummy_train.numpy(), envspec.dummy_reset_table(3, 3))
+    assert np.array_equal(tb.mode._dummy_eval.numpy(), envspec.dummy_reset_table(3, 2))
+    assert tb.mode.c_dummy.reset_count == 3 and tb.mode.c_dummy_eval.reset_count == 2 and tb.mode.c_dummy.time_limit_is_bad == 1
     tb = TaskBatch('MO-Dummy-v0', 1, num_processes=2, num_steps=8, device='cpu', device_env=True, layernorm=True,
                    max_steps=12, bound=1.25, time_limit_is_bad=False, R=3)
-    assert tb.dummy_env and tb.layernorm and (tb.max_steps, tb.bound, tb.time_limit_is_bad, tb.R) == (12, 1.25, False, 3)
+    assert tb.dummy_env and tb.layernorm and (tb.mode.max_steps, tb.mode.bound, tb.mode.time_limit_is_bad, tb.mode.R) == (12, 1.25, False, 3)
     with pytest.raises(PGMError, match='eval_num'):
         TaskBatch('MO-Dummy-v0', 1, device='cpu', eval_num=9)
     with pytest.raises(PGMError, match='must be positive'):

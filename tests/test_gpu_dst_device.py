@@ -85,7 +85,7 @@ def test_fused_rollout_equals_host_stepped(gpu, P, N, kw):
     uni = torch.rand(R, T, N, generator=torch.Generator().manual_seed(4), dtype=torch.float32)
     th, td = _host_batch(pols, N, T, kw), _device_batch(pols, N, T, kw)
     assert td.device_env and td.host_env is None and not hasattr(td, '_h_act')  # no pinned host staging
-    assert td.max_steps == (12 if kw else 50) and td.time_limit_is_bad == bool(kw)
+    assert td.mode.max_steps == (12 if kw else 50) and td.mode.time_limit_is_bad == bool(kw)
     th.env_reset()
     td.env_reset()
     _assert_equal(_snapshot(th), _snapshot(td), 'after env_reset')

@@ -174,7 +174,7 @@ def test_rollout_writes_nothing_else(gpu, K):
     tb._eval_ob[:, P].fill_(SENTINEL)
     before = {k: v.cpu().clone() for k, v in full.items()}
     state, stats, evob = tb._state.cpu().clone(), tb._stats64.cpu().clone(), tb._eval_ob.cpu().clone()
-    tables = tb._dummy_train.cpu().clone(), tb._dummy_eval.cpu().clone()
+    tables = tb.mode._dummy_train.cpu().clone(), tb.mode._dummy_eval.cpu().clone()
     noise = torch.randn(T, N, 2, generator=torch.Generator().manual_seed(1), dtype=torch.float32)
     tb.rollout(0, noise=noise, carry=False)
     tb.rollout(1, noise=None, carry=True)
@@ -187,7 +187,7 @@ def test_rollout_writes_nothing_else(gpu, K):
         assert torch.equal(full[name].cpu(), before[name]), f'{name} was written'
     assert torch.equal(tb._state.cpu(), state), 'parameters / Adam moments were written'
     assert torch.equal(tb._eval_ob.cpu(), evob)
-    assert torch.equal(tb._dummy_train.cpu(), tables[0]) and torch.equal(tb._dummy_eval.cpu(), tables[1])
+    assert torch.equal(tb.mode._dummy_train.cpu(), tables[0]) and torch.equal(tb.mode._dummy_eval.cpu(), tables[1])
     for name, off, w, vec in tb._seg:
         assert torch.equal(tb._stats64[off:off + cap * w].view(cap, w)[P].cpu(),
                            stats[off:off + cap * w].view(cap, w)[P]), f'task row P of {name} was written'

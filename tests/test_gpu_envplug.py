@@ -176,7 +176,7 @@ def test_spare_slot_stays_untouched(gpu, plugins):
     tb._eval_ob[:, P].fill_(SENTINEL)
     before = {k: v.cpu().clone() for k, v in full.items()}
     state, stats, evob = tb._state.cpu().clone(), tb._stats64.cpu().clone(), tb._eval_ob.cpu().clone()
-    tables = tb._plug_train.cpu().clone(), tb._plug_eval.cpu().clone()
+    tables = tb.mode._plug_train.cpu().clone(), tb.mode._plug_eval.cpu().clone()
     noise = _noise(env, N, 1, 1)[0]
     for t in (tb, tc):
         t.rollout(0, noise=noise, carry=False)
@@ -192,7 +192,7 @@ def test_spare_slot_stays_untouched(gpu, plugins):
         assert torch.equal(full[name].cpu(), before[name]), f'{name} was written'
     assert torch.equal(tb._state.cpu(), state), 'parameters / Adam moments were written'
     assert torch.equal(tb._eval_ob.cpu(), evob)
-    assert torch.equal(tb._plug_train.cpu(), tables[0]) and torch.equal(tb._plug_eval.cpu(), tables[1])
+    assert torch.equal(tb.mode._plug_train.cpu(), tables[0]) and torch.equal(tb.mode._plug_eval.cpu(), tables[1])
     for name, off, w, vec in tb._seg:
         assert torch.equal(tb._stats64[off:off + cap * w].view(cap, w)[P].cpu(),
                            stats[off:off + cap * w].view(cap, w)[P]), f'task row P of {name} was written'
@@ -219,10 +219,10 @@ def test_plugdummy_equals_the_builtin_dummy(gpu, plugins, N):
     kw = dict(eval_num=N, raw=False, gamma=0.99)
     tp = _fused(pl, pe.PlugDummy, pols, N, **kw)
     td = _load(TaskBatch('MO-Dummy-v0', P, num_processes=N, num_steps=T, R=R, **kw), pols)
-    assert td.dummy_env and td.max_steps == 500 and td.bound == 5.0 and td.time_limit_is_bad
-    u_train, u_eval = tp._plug_train.clone(), tp._plug_eval.clone()
-    td._dummy_train.copy_(2.0 * u_train - 1.0)
-    td._dummy_eval.copy_(2.0 * u_eval - 1.0)
+    assert td.dummy_env and td.mode.max_steps == 500 and td.mode.bound == 5.0 and td.mode.time_limit_is_bad
+    u_train, u_eval = tp.mode._plug_train.clone(), tp.mode._plug_eval.clone()
+    td.mode._dummy_train.copy_(2.0 * u_train - 1.0)
+    td.mode._dummy_eval.copy_(2.0 * u_eval - 1.0)
     tp.env_reset()
     td.env_reset()
     noise = _noise(pe.PlugDummy, N, 2, 9)

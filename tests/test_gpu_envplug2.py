@@ -231,7 +231,7 @@ def test_spare_slot_stays_untouched(gpu, plugins):
         tb._stats64[off:off + cap * w].view(cap, w)[P].fill_(SENTINEL)
     before = {k: v.cpu().clone() for k, v in full.items()}
     state, stats = tb._state.cpu().clone(), tb._stats64.cpu().clone()
-    consts = [x.cpu().clone() for x in (tb._plug_train, tb._plug_eval, tb._plug_par)]
+    consts = [x.cpu().clone() for x in (tb.mode._plug_train, tb.mode._plug_eval, tb.mode._plug_par)]
     noise = r2.noise(env, N, 1, 1)[0]
     fed = torch.rand(T, N, env.NW, generator=torch.Generator().manual_seed(2), dtype=torch.float64)
     for t in (tb, tc):
@@ -246,7 +246,7 @@ def test_spare_slot_stays_untouched(gpu, plugins):
     for name in ('returns', 'adv'):
         assert torch.equal(full[name].cpu(), before[name]), f'{name} was written'
     assert torch.equal(tb._state.cpu(), state), 'parameters / Adam moments were written'
-    for x, y in zip((tb._plug_train, tb._plug_eval, tb._plug_par), consts):
+    for x, y in zip((tb.mode._plug_train, tb.mode._plug_eval, tb.mode._plug_par), consts):
         assert torch.equal(x.cpu(), y)
     assert torch.equal(tb.env_noise.cpu(), fed), 'the fed env noise was written'
     for name, off, w, vec in tb._seg:

@@ -70,7 +70,7 @@ def host_case(gpu, request):
     tb.noise.copy_(noise)
     rows = tb.obs[:, 0].clone()
     tb._rollout_act(0)
-    out = {'slot': (tb.values[:, 0], tb.actions[:, 0], tb.logp[:, 0]), 'action_out': tb._d_act[:P],
+    out = {'slot': (tb.values[:, 0], tb.actions[:, 0], tb.logp[:, 0]), 'action_out': tb.mode._d_act[:P],
            'act': tb.act(rows, noise[0]), 'det': tb.act(rows, deterministic=True)}
     d = Dims(P, 1, 0, tb.O, tb.A, tb.K, tb.H, int(tb.layernorm))
     if tb.discrete:

@@ -170,8 +170,9 @@ def test_set_task_hparams_refused_on_other_batch_kinds():
         with pytest.raises(PGMError, match=flag):
             tb.set_task_hparams(clip_param=0.1)
     # the kinds that need a host env or a compiled header to exist: the flags set_task_hparams looks at, on a plain batch
-    for attr, val, flag in (('any_dims', True, 'any_dims'), ('plugin', object(), 'env_plugin'),
-                            ('device_env', True, 'device_env'), ('host_env', object(), 'host_env'),
+    from pgmorl_amd.runtime import DstMode, HostMode, PluginMode
+    for attr, val, flag in (('any_dims', True, 'any_dims'), ('mode', PluginMode, 'env_plugin'),
+                            ('mode', DstMode, 'device_env'), ('mode', HostMode, 'host_env'),
                             ('discrete', True, 'discrete')):
         tb = _cpu_batch(2)
         setattr(tb, attr, val)

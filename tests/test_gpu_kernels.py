@@ -268,14 +268,19 @@ def _oracle_rollout(pol, envs, ro, noise):
         ro.value_preds[-1] = pol.get_value(ro.obs[-1])
 
 
-def _teacher_forced_check(tb, p, pol, spec, s0, noise):
+def _teacher_forced_check(tb, p, pol, spec, s0, noise, gamma=0.995, ob_rms=True, obj_rms=True, stats=None):
     """Per-step parity from the device's own trajectory: policy(device obs[t]) vs device action / log-prob /
     value, and the oracle VecNormalized env stepped with the device's actions vs device obs[t+1], rewards,
-    masks (its fp64 env state then tracks the device's to fp64 rounding, so nothing compounds)."""
+    masks (its fp64 env state then tracks the device's to fp64 rounding, so nothing compounds).
+    gamma, ob_rms, obj_rms: the oracle env's settings (the batch's); stats: {'ob_rms' / 'ret_rms' / 'obj_rms':
+    RunningMeanStd} preloaded into the oracle env (copies) before its reset.  A switched-off statistic is not compared.
+    -> the oracle env after the last step."""
     T, N = tb.T, tb.N
     obs = tb.obs[p].cpu().double()
     acts = tb.actions[p].cpu().double()
-    envs = VecNormalizedSynth(spec, s0, 0.995)
+    envs = VecNormalizedSynth(spec, s0, gamma, ob_rms, obj_rms)
+    for key, r in (stats or {}).items():
+        setattr(envs, key, r.copy())
     _close(obs[0], envs.reset(), 5e-5, 1e-4, 'obs[0]')
     for t in range(T):
         with torch.no_grad():
@@ -291,8 +296,11 @@ def _teacher_forced_check(tb, p, pol, spec, s0, noise):
                                       [0.0 if 'bad_transition' in i else 1.0 for i in infos])
     with torch.no_grad():
         _close(tb.values[p, T].cpu(), pol.get_value(obs[T]), 5e-5, 1e-4, 'bootstrap value')
-    _close(tb.obj_var[p].cpu(), envs.obj_rms.var, 0, 1e-6, 'obj_rms.var')
-    _close(tb.ob_var[p].cpu(), envs.ob_rms.var, 1e-9, 1e-6, 'ob_rms.var')
+    if obj_rms:
+        _close(tb.obj_var[p].cpu(), envs.obj_rms.var, 0, 1e-6, 'obj_rms.var')
+    if ob_rms:
+        _close(tb.ob_var[p].cpu(), envs.ob_rms.var, 1e-9, 1e-6, 'ob_rms.var')
+    return envs
 
 
 @pytest.mark.parametrize('kernel', ['lanes', 'block'])
